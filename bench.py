@@ -10,8 +10,15 @@ actions are drawn on the device (Philox4x32-10 keyed by (seed=1001, global env i
 examples/random_actions.py semantics).  Inputs are resident in HBM before the timed region; host
 buffers are not touched inside it.
 
-  python bench.py [--task T] [--gpus N] [--steps K] [--warmup W] [--envs E_per_gpu]
+  python bench.py [--task T] [--gpus N] [--steps K] [--warmup W] [--envs E_per_gpu] [--full] [--dump-outputs DIR]
   torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds what
+takes runs of its own: the per-step API's rate (step_sync), the per-kernel event pass and the
+roofline figures, the CPU baseline, the other single-GPU tasks, the policy-evaluation loop and the
+detail side file.  --dump-outputs DIR writes what the last timed step returned (obs, reward, done,
+info of every env of rank 0) as DIR/<name>.npy (float32); inputs are seeded, so two builds run
+with the same arguments can be compared array for array.
 
 Multi-GPU: envs shard across ranks (global env id = rank*E + e, independent units -> weak
 scaling); rollouts (obs, reward, done, info) are collected with an RCCL all-gather over xGMI
@@ -138,6 +145,21 @@ def pmc_summary(name, kernels, ms_per_step, E):
     return out
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write name -> array (torch tensor or ndarray) as <dirname>/<name>.npy in
+    float32 (float64 arrays stay float64).  The outputs of one step of every env are a few hundred
+    kB at the default sizes, far below the 64 MB an output dump may hold."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        total += a.nbytes
+        assert total <= 64 << 20, 'output dump above 64 MB'
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def facade_bench(args):
     """Trainer-side throughput: AVRTorchVecEnv.step with device actions, auto-reset on (every env
     ends its episode at the 200-step TimeLimit, then resets: FeedingJaco with the device IK whose
@@ -176,13 +198,17 @@ def facade_bench(args):
             torch.cuda.synchronize(dev)
             t_drain.append(time.perf_counter() - td)
         ts = time.perf_counter()
-        _, _, _, info = v.step(act)
+        last = v.step(act)
+        info = last[3]
         if 'terminal_observation' in info:
             roll += 1
             t_roll.append(time.perf_counter() - ts)
     torch.cuda.synchronize(dev)
     el = time.perf_counter() - t0
     captures = v.sim.graph_captures() - c0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'obs': last[0], 'reward': last[1], 'done': last[2],
+                                         'total_force_on_human': info['total_force_on_human'], 'task_success': info['task_success']})
     # the same loop over steps that end no episode (synchronised at both ends, after the next
     # episode's reset draws are ready so that no prefetch runs beside it)
     if v._prefetch:
@@ -231,7 +257,9 @@ T_START = time.perf_counter()
 
 def run_task(name, args, steps, warmup, world, rank, local, dist, gloo, dev, cpu_seconds):
     """Time `steps` gym steps of task `name` (E = args.envs per GPU) after `warmup` untimed ones;
-    returns the JSON object of its bench line (cpu_baseline when cpu_seconds > 0)."""
+    returns the JSON object of its bench line and, with --full, the detail record (else None).
+    --full adds the passes that follow the timed steps: the per-step API's rate, the per-kernel
+    event pass with the roofline figures, and the CPU baseline when cpu_seconds > 0."""
     import numpy as np
     progress('%s: reset pool' % name)
     import torch
@@ -324,6 +352,44 @@ def run_task(name, args, steps, warmup, world, rank, local, dist, gloo, dev, cpu
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
     t_next = warmup + steps
+    value = world * E * steps / el
+    ms_per_step = el / steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # what the last timed step wrote for this rank's envs (multi-GPU rollouts: its row of the
+        # stacked per-step outputs)
+        if world > 1 and not args.step_sync:
+            j = (steps - 1) % G
+            last = {'obs': so[j], 'reward': sr[j], 'done': sd[j], 'info': si[j]}
+        else:
+            last = {'obs': obs, 'reward': rew, 'done': done, 'info': info}
+        dump_outputs(args.dump_outputs, last)
+
+    def headline(St):
+        flags = St[:, L.S_TASK + L.T_FLAGS].astype(np.int64)
+        return flags, {
+            'metric': 'env-steps/sec at N parallel envs, 1/2/4/8 MI355X; max |dq| vs PyBullet',
+            'value': value,
+            'unit': 'env-steps/s',
+            'n_gpus': world,
+            'steps': steps,
+            'warmup': warmup,
+            'ms_per_step': ms_per_step,
+            'higher_is_better': True,
+            'scaling': 'weak',
+            'vs_baseline': None,
+            'dtype': 'f32',
+            'data': 'synthetic: random actions U(-1,1)^7 (Philox, device), reset states from the reset path (%d distinct per GPU, tiled)' % pool,
+            'config': {'workload': T['workload'] % E, 'task': name, 'envs_per_gpu': E, 'impairment': args.impairment,
+                       'parallelism': 'env-sharded x%d' % world, 'env_groups': sim.env_groups(),
+                       'stepping': 'per-step joins' if args.step_sync else ('rollout' if world == 1 else 'rollout x%d steps' % G)},
+            # fault bits only (bits 0-4); bit 5 (an env under the EPA budget) is informational
+            'nan_or_overflow_envs': int(np.count_nonzero(flags & _lib.FLAGS_FAULT_MASK)),
+        }
+
+    if not args.full:
+        _, out = headline(sim.get_state())
+        sim.close()
+        return out, None
     # the per-step API's rate beside the rollout headline (avr_step_random_device, env groups
     # joined after every step): what a policy in the loop gets (enjoy_vr.py:106-116, a PPO
     # rollout), which needs every step's observation before it can act
@@ -354,11 +420,9 @@ def run_task(name, args, steps, warmup, world, rank, local, dist, gloo, dev, cpu
     step_kernel_ms = sum(v['ms_per_step'] for v in kernels.values())
     dominant = max(kernels, key=lambda k: kernels[k]['ms_per_step'])
     St = sim.get_state()
-    flags = St[:, L.S_TASK + L.T_FLAGS].astype(np.int64)
-    value = world * E * steps / el
+    flags, out = headline(St)
     bpe = T['bytes']
     achieved = bpe * E / (step_kernel_ms * 1e-3) / 1e9
-    ms_per_step = el / steps * 1e3
     pmc = pmc_summary(name, [k for k, v in kt.items() if v[1] > 0], ms_per_step, E)
     traffic = pmc['traffic'] if pmc else None
     # the bound: the larger of the two roofline fractions the path could sit on (HBM bytes vs the
@@ -372,31 +436,12 @@ def run_task(name, args, steps, warmup, world, rank, local, dist, gloo, dev, cpu
         q = pmc['sq'][dominant]
         limiter = 'latency (waves waiting %.0f%% of their cycles, issuing %.0f%%)' % (100 * q['wait_frac'], 100 * q['issue_frac']) \
             if q['wait_frac'] > q['issue_frac'] else 'instruction issue (%.0f%% of wave cycles)' % (100 * q['issue_frac'])
-    out = {
-        'metric': 'env-steps/sec at N parallel envs, 1/2/4/8 MI355X; max |dq| vs PyBullet',
-        'value': value,
-        'unit': 'env-steps/s',
-        'n_gpus': world,
-        'steps': steps,
-        'warmup': warmup,
-        'ms_per_step': ms_per_step,
-        'higher_is_better': True,
-        'scaling': 'weak',
-        'vs_baseline': None,
-        'dtype': 'f32',
-        'data': 'synthetic: random actions U(-1,1)^7 (Philox, device), reset states from the reset path (%d distinct per GPU, tiled)' % pool,
-        'config': {'workload': T['workload'] % E, 'task': name, 'envs_per_gpu': E, 'impairment': args.impairment,
-                   'parallelism': 'env-sharded x%d' % world, 'env_groups': sim.env_groups(),
-                   'stepping': 'per-step joins' if args.step_sync else ('rollout' if world == 1 else 'rollout x%d steps' % G)},
-        'step_sync': step_sync,
-        'roofline': {'bound': bound, 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                     'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic, 'limiter': limiter,
-                     'valu_busy': pmc.get('valu_busy_chip') if pmc else None,
-                     'bytes_per_env_step': bpe, 'dominant_kernel': dominant,
-                     'dominant_avg_ms': kernels[dominant]['avg_ms']},
-        # fault bits only (bits 0-4); bit 5 (an env under the EPA budget) is informational
-        'nan_or_overflow_envs': int(np.count_nonzero(flags & _lib.FLAGS_FAULT_MASK)),
-    }
+    out['step_sync'] = step_sync
+    out['roofline'] = {'bound': bound, 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                       'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic, 'limiter': limiter,
+                       'valu_busy': pmc.get('valu_busy_chip') if pmc else None,
+                       'bytes_per_env_step': bpe, 'dominant_kernel': dominant,
+                       'dominant_avg_ms': kernels[dominant]['avg_ms']}
     # the long-form record (per-kernel tables, PMC issue shares, the scope of each figure) goes to
     # a side file, so that the printed line stays within the driver's record
     detail = {'task': name, 'value': value, 'ms_per_step': ms_per_step, 'roofline_fracs': fracs,
@@ -485,6 +530,8 @@ def policy_eval_bench(args):
     name = args.task
     E = args.envs if args.envs is not None else TASKS[name].get('envs', 4096)
     r, total = policy_eval_run(name, E)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: r[k] for k in ('returns', 'mean_force', 'task_success', 'done')})
     out = {'metric': 'policy-eval env-steps/sec (avr.policy_eval.evaluate: enjoy_vr.py loop, fresh action tensor per step)',
            'value': E * 200 / r['loop_s'], 'unit': 'env-steps/s', 'n_gpus': 1, 'steps': 200, 'warmup': 0,
            'ms_per_step': r['loop_s'] / 200 * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
@@ -504,6 +551,14 @@ def main():
     ap.add_argument('--envs', type=int, default=None, help='envs per GPU (default: the config\'s, 4096; DressingJaco 2048)')
     ap.add_argument('--settle', type=int, default=None, help='reset settle frames (FeedingJaco 100, ScratchItch 0)')
     ap.add_argument('--gather-every', type=int, default=16)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run what takes runs of its own: the per-step API rate (--sync-steps), '
+                         'the per-kernel event pass and roofline figures, the CPU baseline (--cpu-seconds), the other '
+                         'single-GPU tasks (--other-steps), the policy-evaluation loop (--policy-eval-steps), and write '
+                         'the detail side file; those options have no effect without it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last of them returned (obs, reward, done, info of every '
+                         'env; rank 0) as DIR/<name>.npy, float32')
     ap.add_argument('--step-sync', action='store_true',
                     help='time avr_step_random_device per step (env groups joined after every step) instead of rollouts')
     ap.add_argument('--sync-steps', type=int, default=20,
@@ -533,6 +588,8 @@ def main():
     ap.add_argument('--impairment', default='random',
                     help="human impairment per env: 'random' is the tasks' own setting (feeding.py:175, scratch_itch.py:178)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if args.facade:
         return facade_bench(args)
     if args.policy_eval:
@@ -555,9 +612,16 @@ def main():
         else:
             dist.init_process_group('nccl', device_id=torch.device('cuda', local))
     dev = torch.device('cuda', local)
-    cpu_s = 0.0 if args.no_cpu_baseline else args.cpu_seconds
+    cpu_s = 0.0 if args.no_cpu_baseline or not args.full else args.cpu_seconds
     out, det = run_task(args.task, args, args.steps, args.warmup, world, rank, local, dist, gloo, dev, cpu_s)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out, separators=(',', ':')), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     details = [det]
+    args.dump_outputs = None         # the dump is of the headline task's timed steps only
     if rank == 0 and world == 1 and args.task == 'FeedingJaco-v0' and args.other_steps > 0:
         out['other_tasks'] = {}
         for name in OTHER_TASKS:

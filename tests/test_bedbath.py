@@ -23,7 +23,6 @@ import pytest
 from avr import _abi as ABI
 
 BB = ABI.BB
-REF = '/root/reference/assistive_gym/envs/assets'
 # bed_bathing.py:232: joint_angles of the VR/replay bed bathing.  The reference applies them to
 # joints range(7) (:233), but the seven values are the right arm's settled pose (joints 7..13):
 # the non-VR settle below reproduces them within 0.012 rad, which no other joint set comes near
@@ -98,9 +97,12 @@ def test_bed_and_wiper(bb):
     np.testing.assert_allclose(A['bb_human_base'][:3], [0, 0, 0.7])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference assets not mounted (GPU box)')
-def test_committed_bedbath_scene_matches_compiler(tmp_path):
+def test_committed_bedbath_scene_matches_compiler(tmp_path, monkeypatch):
+    """The compiler run on the committed asset cache (avr/data/asset_cache.npz, read afresh here)
+    writes the committed npz."""
     from avr import model_compiler as MC
+    monkeypatch.setattr(MC, '_asset_memo', None)
+    monkeypatch.setattr(MC, 'REF_ASSETS', os.path.join(os.path.dirname(__file__), 'no_such_assets'))
     _, A = MC.compile_bedbath(str(tmp_path))
     B = ABI.load_scene(ABI.TASK_BEDBATH)
     assert set(A) == set(B)

@@ -16,7 +16,6 @@ import pytest
 from avr import _abi as ABI
 
 SI = ABI.SI
-REF = '/root/reference/assistive_gym/envs/assets'
 
 
 @pytest.fixture(scope='module')
@@ -89,10 +88,13 @@ def test_scratch_pairs_and_chain(sc):
             assert sh_body not in (a, b)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference assets not mounted (GPU box)')
-def test_committed_scratch_scene_matches_compiler():
+def test_committed_scratch_scene_matches_compiler(monkeypatch):
+    """The compiler run on the committed asset cache (avr/data/asset_cache.npz, read afresh here)
+    writes the committed npz."""
     import tempfile
     from avr import model_compiler as MC
+    monkeypatch.setattr(MC, '_asset_memo', None)
+    monkeypatch.setattr(MC, 'REF_ASSETS', os.path.join(os.path.dirname(__file__), 'no_such_assets'))
     with tempfile.TemporaryDirectory() as d:
         path, A = MC.compile_scratch(d)
         committed = np.load(os.path.join(MC.DATA_DIR, 'scratch_itch_pr2.npz'))

@@ -6,11 +6,12 @@ set -o pipefail
 cd /root/repo && export TMPDIR=/tmp && mkdir -p gpurun_out/var
 VS=${VARIANTS:-default}
 T=${TASK:-FeedingJaco-v0}
+O=${AB_OUT:-$(mktemp -d)} && mkdir -p $O      # bench lines and their stderr; the summary is printed
 for r in 1 2; do
   for v in $VS; do
     L=""
     if [ $v != default ]; then L=/root/repo/exp/libavr_$v.so; fi
-    AVR_LIB=$L timeout -k 10 200 python3 bench.py --task $T --steps 30 --warmup 3 --no-cpu-baseline > gpurun_out/var/b_${v}_$r.json 2> gpurun_out/var/b_${v}_$r.err || exit $?
-    echo $T $v $r $(python3 -c "import json;d=json.loads(open('gpurun_out/var/b_${v}_$r.json').read().strip().splitlines()[-1]);k=d['roofline']['kernels'];print(round(d['value']), d['nan_or_overflow_envs'], {n[4:16]:round(x['avg_ms'],4) for n,x in k.items()})")
+    AVR_LIB=$L timeout -k 10 200 python3 bench.py --task $T --steps 30 --warmup 3 --no-cpu-baseline > $O/b_${v}_$r.json 2> $O/b_${v}_$r.err || exit $?
+    echo $T $v $r $(python3 -c "import json;d=json.loads(open('$O/b_${v}_$r.json').read().strip().splitlines()[-1]);print(round(d['value']), d['nan_or_overflow_envs'])")
   done
 done
