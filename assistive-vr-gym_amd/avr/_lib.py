@@ -21,6 +21,7 @@ EXPORTS = [
     'avr_hull_support_table', 'avr_task', 'avr_task_state_words', 'avr_task_obs_dim', 'avr_task_act_dim', 'avr_n_dof',
     'avr_get_q', 'avr_get_link_pose', 'avr_get_contact_summary', 'avr_get_flags', 'avr_reset_ik', 'avr_base_search',
     'avr_graph_captures', 'avr_robot_self_contact', 'avr_narrowphase_query',
+    'avr_policy_set', 'avr_policy_act_device', 'avr_rollout_policy_device',
 ]
 FLAGS_FAULT_MASK = 0x1f      # include/avr.h AVR_FLAGS_FAULT_MASK: bits 0-4; bit 5 (EPA budget) is informational
 
@@ -31,6 +32,13 @@ FLAGS_FAULT_MASK = 0x1f      # include/avr.h AVR_FLAGS_FAULT_MASK: bits 0-4; bit
 class avr_config(C.Structure):
     _fields_ = [('n_envs', C.c_int32), ('device', C.c_int32), ('env_offset', C.c_int32), ('flags', C.c_int32),
                 ('seed', C.c_uint64)]
+
+
+class avr_policy_desc(C.Structure):
+    """include/avr.h avr_policy_desc: host float32 arrays, matrices row-major [out][in]."""
+    ARRAYS = ('ob_mean', 'ob_var', 'a_w1', 'a_b1', 'a_w2', 'a_b2', 'mu_w', 'mu_b', 'logstd', 'c_w1', 'c_b1', 'c_w2', 'c_b2', 'c_w3', 'c_b3')
+    _fields_ = [('obs_dim', C.c_int32), ('act_dim', C.c_int32), ('hidden', C.c_int32), ('n_layers', C.c_int32),
+                ('clip_obs', C.c_float), ('eps', C.c_float)] + [(k, C.c_void_p) for k in ARRAYS]
 
 
 _LIB = None
@@ -64,6 +72,10 @@ def load(path=LIB_PATH):
     lib.avr_step_random_device.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
     lib.avr_rollout_random_device.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, vp, C.c_int32]
     lib.avr_random_actions_device.argtypes = [vp, C.c_int64, vp]
+    if hasattr(lib, 'avr_policy_set'):              # (absent in experiment builds of older trees)
+        lib.avr_policy_set.argtypes = [vp, C.POINTER(avr_policy_desc)]
+        lib.avr_policy_act_device.argtypes = [vp, C.c_int64, vp, C.c_int32, vp, vp, vp]
+        lib.avr_rollout_policy_device.argtypes = [vp, C.c_int64, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     lib.avr_sync.argtypes = [vp]
     lib.avr_stream.argtypes = [vp]
     lib.avr_stream.restype = vp
@@ -269,6 +281,34 @@ class Sim:
     def random_actions_device(self, t, d_act):
         self._chk(self.lib.avr_random_actions_device(self.h, int(t), d_act))
 
+    # ---- the policy on the device (include/avr.h avr_policy_*)
+    def policy_set(self, desc):
+        """Install a policy: desc is policy_eval.policy_desc's dict (obs_dim, act_dim, hidden,
+        n_layers, clip_obs, eps and the float32 arrays of avr_policy_desc.ARRAYS, None = absent).
+        Later calls overwrite the weights in stream order; no graph is re-captured."""
+        d = avr_policy_desc(obs_dim=int(desc['obs_dim']), act_dim=int(desc['act_dim']), hidden=int(desc['hidden']),
+                            n_layers=int(desc.get('n_layers', 2)), clip_obs=float(desc.get('clip_obs', 10.0)), eps=float(desc.get('eps', 1e-8)))
+        keep = []
+        for k in avr_policy_desc.ARRAYS:
+            a = desc.get(k)
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float32)
+                keep.append(a)
+                setattr(d, k, a.ctypes.data)
+        self._chk(self.lib.avr_policy_set(self.h, C.byref(d)))
+
+    def policy_act_device(self, t, d_obs, deterministic, d_act, d_logp=None, d_value=None):
+        """One forward over all envs at step index t (device pointers; d_act None: the value alone)."""
+        self._chk(self.lib.avr_policy_act_device(self.h, int(t), d_obs, int(bool(deterministic)), d_act, d_logp, d_value))
+
+    def rollout_policy_device(self, t0, n, d_obs0, deterministic, d_obs, d_act, d_logp, d_value, d_rew, d_done, d_info):
+        """n steps from step index t0 with the installed policy in the loop (= n x {policy_act_device;
+        step_device}, bit for bit): d_obs0 (None: the handle's observation buffer) is what step t0's
+        policy sees; d_obs [n+1, E, obs], d_value [n+1, E] (or None), d_act / d_logp (or None) / d_rew /
+        d_done / d_info [n, E, ...] are stacked device arrays."""
+        self._chk(self.lib.avr_rollout_policy_device(self.h, int(t0), int(n), d_obs0, int(bool(deterministic)), d_obs, d_act, d_logp, d_value,
+                                                     d_rew, d_done, d_info))
+
     def sync(self):
         self._chk(self.lib.avr_sync(self.h))
 
@@ -364,6 +404,31 @@ def random_actions(seed, env_ids, t, act_dim=ABI.ACT_DIM):
             if j < act_dim:
                 x = (r[k] >> np.uint64(8)).astype(np.float32)
                 out[:, j] = x * np.float32(1.0 / 16777216.0) * np.float32(2.0) - np.float32(1.0)
+    return out
+
+
+def policy_noise(seed, env_ids, t, act_dim=ABI.ACT_DIM):
+    """eps[e, j] ~ N(0, 1), float64: the host mirror of the device policy's sampling noise
+    (csrc/avr_policy.hip philox_normal).  Philox4x32-10 keyed by (seed, env, t) as random_actions,
+    with the top bit of counter word 2 set (random_actions' word 2 is j >> 2: never set), so the
+    two streams share no counter.  Block j >> 2 gives four words; words (0, 1) make the Box-Muller
+    pair of j & 3 = 0 (cos) and 1 (sin), words (2, 3) that of j & 3 = 2 and 3, with
+    u1 = ((x >> 8) + 0.5) / 2^24 formed in float32 as on the device (never 0) and
+    u2 = (x' >> 8) / 2^24; the logarithm, root and cos / sin are float64 here."""
+    env_ids = np.asarray(env_ids, np.uint64)
+    out = np.zeros((len(env_ids), act_dim), np.float64)
+    for blk in range((act_dim + 3) // 4):
+        c = [env_ids, np.full_like(env_ids, t & 0xFFFFFFFF), np.full_like(env_ids, 0x80000000 | blk), np.full_like(env_ids, (t >> 32) & 0xFFFFFFFF)]
+        r = philox4x32_10(c, seed, seed >> 32)
+        for pair in range(2):
+            xa, xb = r[2 * pair] >> np.uint64(8), r[2 * pair + 1] >> np.uint64(8)
+            u1 = ((xa.astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)).astype(np.float64)
+            u2 = xb.astype(np.float64) / 16777216.0
+            rad, th = np.sqrt(-2.0 * np.log(u1)), 2.0 * np.pi * u2
+            for k, z in ((0, rad * np.cos(th)), (1, rad * np.sin(th))):
+                j = 4 * blk + 2 * pair + k
+                if j < act_dim:
+                    out[:, j] = z
     return out
 
 

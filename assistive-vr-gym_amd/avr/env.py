@@ -446,10 +446,14 @@ class AVRTorchVecEnv(AVRVecEnv):
         self.t_rew = torch.zeros(n, device=self.dev)
         self.t_done = torch.zeros(n, dtype=torch.uint8, device=self.dev)
         self.t_info = torch.zeros(n, ABI.INFO_DIM, device=self.dev)
+        self._cur = None                   # the current observation (what reset / step / rollout_policy last returned)
+        self._roll = {}                    # rollout_policy's stacked output buffers, by rollout length
+        self.policy_t = 0                  # rollout_policy's step index (keys the sampling noise; never reused)
 
     def reset(self, mask=None):
         obs = super().reset(mask)
         self.t_obs.copy_(self.torch.from_numpy(obs))
+        self._cur = self.t_obs.clone()
         return self.t_obs.clone()
 
     def step(self, actions):
@@ -474,7 +478,67 @@ class AVRTorchVecEnv(AVRVecEnv):
                 self._reset_rows(dh)
                 m = torch.from_numpy(dh).to(self.dev)
                 obs = torch.where(m[:, None], torch.from_numpy(self._obs).to(self.dev), obs)
+        self._cur = obs
         return obs, rew, done, info
+
+    # ------------------------------------------------------------------ device-resident policy rollouts
+    def set_policy(self, actor_critic, ob_rms):
+        """Install (or, after an update of its weights, re-install) the policy rollout_policy runs:
+        an ActorCritic and its ob_rms (None: no normalisation), packed by policy_eval.policy_desc.
+        No graph is re-captured."""
+        from .policy_eval import policy_desc
+        self.sim.policy_set(policy_desc(actor_critic, ob_rms, self.L.OBS_DIM, self.L.ACT_DIM))
+
+    def rollout_policy(self, actor_critic, ob_rms, n, deterministic=False):
+        """n steps with the policy on the device, from the env's current observation, in one call
+        with no host work per step (include/avr.h avr_rollout_policy_device).  actor_critic None:
+        the policy installed by the last set_policy / rollout_policy call (pass it again after
+        every weight update).  With auto_reset, n is capped so that the rollout ends at the
+        TimeLimit at the latest, and finished episodes are rolled over after the call, as step does.
+
+        Returns a dict of device tensors, stacked over the steps actually run, out['n']:
+        obs [n+1, E, obs_dim] (slot 0 the current observation, slot k+1 the one after step k),
+        act [n, E, act_dim], logp [n, E], value [n+1, E] (slot k = V(obs[k])), rew [n, E],
+        done [n, E] uint8, info [n, E, 2] = {total_force_on_human, task_success}, and reset, the
+        [E] bool mask of the envs rolled over after the call (None: none; obs[n] stays their
+        terminal observation, the next rollout starts from their reset one).  The tensors are the
+        env's own buffers, one set per rollout length: the next rollout of that length overwrites them."""
+        torch = self.torch
+        if self._cur is None:
+            raise RuntimeError('rollout_policy: reset() the env first')
+        if actor_critic is not None:
+            self.set_policy(actor_critic, ob_rms)
+        n = int(n)
+        if self.auto_reset:
+            n = min(n, int(self.max_steps - self.iteration.max()))
+        if n < 1:
+            raise ValueError('rollout_policy: n must be >= 1')
+        E, L = self.n, self.L
+        B = self._roll.get(n)
+        if B is None:
+            z = lambda *shape, **kw: torch.zeros(*shape, device=self.dev, **kw)
+            B = self._roll[n] = dict(obs=z(n + 1, E, L.OBS_DIM), act=z(n, E, L.ACT_DIM), logp=z(n, E), value=z(n + 1, E), rew=z(n, E),
+                                     done=z(n, E, dtype=torch.uint8), info=z(n, E, ABI.INFO_DIM))
+        cur = self._cur.to(self.dev, torch.float32).contiguous()
+        self.ext.wait_stream(torch.cuda.current_stream(self.dev))
+        self.sim.rollout_policy_device(self.policy_t, n, cur.data_ptr(), deterministic,
+                                       B['obs'].data_ptr(), B['act'].data_ptr(), B['logp'].data_ptr(), B['value'].data_ptr(),
+                                       B['rew'].data_ptr(), B['done'].data_ptr(), B['info'].data_ptr())
+        torch.cuda.current_stream(self.dev).wait_stream(self.ext)
+        self.iteration += n
+        self.policy_t += n
+        out = dict(B, n=n, reset=None)
+        self._cur = B['obs'][n].clone()
+        if self.auto_reset:
+            dh = self.iteration >= self.max_steps
+            if dh.any():
+                torch.cuda.current_stream(self.dev).synchronize()
+                self.episode[dh] += 1
+                self._reset_rows(dh)
+                m = torch.from_numpy(dh).to(self.dev)
+                self._cur = torch.where(m[:, None], torch.from_numpy(self._obs).to(self.dev), self._cur)
+                out['reset'] = m
+        return out
 
     def close(self):
         self.torch.cuda.synchronize(self.dev)

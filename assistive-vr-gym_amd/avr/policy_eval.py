@@ -97,6 +97,50 @@ def load_policy(path, device='cpu'):
     return pol, rms
 
 
+POLICY_MAX_HIDDEN = 64              # csrc/avr_policy.hip POL_H
+
+
+def policy_desc(actor_critic, ob_rms, obs_dim=None, act_dim=None):
+    """The descriptor of the device policy (include/avr.h avr_policy_desc, _lib.Sim.policy_set) of
+    an ActorCritic and its ob_rms (None: no normalisation): a dict of the dimensions, clip_obs / eps
+    and float32 host arrays in torch.nn.Linear's [out][in] orientation.  Raises ValueError for a
+    policy the kernel does not take: anything but two tanh layers of at most 64 units per network,
+    or dimensions other than obs_dim / act_dim (the env's) when those are given."""
+    def lin(m, n_out, n_in, what):
+        if not isinstance(m, torch.nn.Linear) or m.bias is None or tuple(m.weight.shape) != (n_out, n_in):
+            raise ValueError('policy_desc: %s must be a Linear(%d, %d) with bias, got %r' % (what, n_in, n_out, m))
+        return m.weight.detach().cpu().numpy().astype(np.float32), m.bias.detach().cpu().numpy().astype(np.float32)
+
+    def trunk(seq, n, what):
+        mods = list(seq)
+        if len(mods) != n or not all(isinstance(mods[i], torch.nn.Tanh) for i in (1, 3)):
+            raise ValueError('policy_desc: %s must be Linear, Tanh, Linear, Tanh%s (two hidden layers)' % (what, ', Linear' if n == 5 else ''))
+        return mods
+
+    od, ad, h = int(actor_critic.obs_dim), int(actor_critic.act_dim), int(actor_critic.hidden)
+    if not 1 <= h <= POLICY_MAX_HIDDEN:
+        raise ValueError('policy_desc: hidden %d outside 1..%d' % (h, POLICY_MAX_HIDDEN))
+    if (obs_dim is not None and od != int(obs_dim)) or (act_dim is not None and ad != int(act_dim)):
+        raise ValueError('policy_desc: policy is %d -> %d, the env needs %s -> %s' % (od, ad, obs_dim, act_dim))
+    a, c = trunk(actor_critic.actor, 4, 'actor'), trunk(actor_critic.critic, 5, 'critic')
+    d = dict(obs_dim=od, act_dim=ad, hidden=h, n_layers=2, clip_obs=CLIP_OBS, eps=EPS, ob_mean=None, ob_var=None)
+    d['a_w1'], d['a_b1'] = lin(a[0], h, od, 'actor[0]')
+    d['a_w2'], d['a_b2'] = lin(a[2], h, h, 'actor[2]')
+    d['mu_w'], d['mu_b'] = lin(actor_critic.mu, ad, h, 'mu')
+    d['logstd'] = actor_critic.logstd.detach().cpu().numpy().astype(np.float32).reshape(-1)
+    if d['logstd'].shape != (ad,):
+        raise ValueError('policy_desc: logstd must have %d entries' % ad)
+    d['c_w1'], d['c_b1'] = lin(c[0], h, od, 'critic[0]')
+    d['c_w2'], d['c_b2'] = lin(c[2], h, h, 'critic[2]')
+    d['c_w3'], d['c_b3'] = lin(c[4], 1, h, 'critic[4]')
+    if ob_rms is not None:
+        m, v = np.asarray(ob_rms.mean, np.float32).reshape(-1), np.asarray(ob_rms.var, np.float32).reshape(-1)
+        if m.shape != (od,) or v.shape != (od,):
+            raise ValueError('policy_desc: ob_rms has %d / %d entries, the policy sees %d' % (m.size, v.size, od))
+        d['ob_mean'], d['ob_var'] = m, v
+    return d
+
+
 def _graphed_policy(actor_critic, ob_rms, obs, hxs, masks, deterministic):
     """The policy forward captured once into a torch CUDA (HIP) graph with static obs / masks
     buffers; returns step(obs, masks) -> action (a fresh tensor per step), or None when capture is
@@ -124,7 +168,43 @@ def _graphed_policy(actor_critic, ob_rms, obs, hxs, masks, deterministic):
     return step
 
 
-def evaluate(env_id, actor_critic, ob_rms, n_envs=64, steps=200, deterministic=True, setup=None, device=0, seed=1001, graph=False):
+FUSED_CHUNK = 50                    # steps per rollout_policy call of evaluate(fused=True)
+
+
+def _evaluate_fused(env, actor_critic, ob_rms, steps, deterministic):
+    """evaluate()'s loop as device-resident rollouts (AVRTorchVecEnv.rollout_policy): the policy
+    runs inside the rollout graphs, FUSED_CHUNK steps per call, and the per-env sums are taken from
+    the stacked outputs.  The graphs are captured by one untimed chunk, after which the state is put
+    back (the eager path's untimed forward, for graphs); the noise is the device's Philox stream,
+    not torch's."""
+    dev, n_envs = env.dev, env.n
+    env.reset()
+    env.set_policy(actor_critic, ob_rms)
+    ret = torch.zeros(n_envs, device=dev)
+    force = torch.zeros(n_envs, device=dev)
+    chunk = min(FUSED_CHUNK, steps)
+    if chunk > 0:
+        S, cur = env.get_state(), env._cur.clone()
+        env.rollout_policy(None, None, chunk, deterministic)
+        env.set_state(S)
+        env._cur = cur
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    out, k = None, 0
+    while k < steps:
+        out = env.rollout_policy(None, None, min(chunk, steps - k), deterministic)
+        ret += out['rew'].sum(0)
+        force += out['info'][:, :, 0].sum(0)
+        k += out['n']
+    torch.cuda.synchronize(dev)
+    loop_s = time.perf_counter() - t0
+    return dict(returns=ret.cpu().numpy(), mean_force=(force / max(steps, 1)).cpu().numpy(),
+                task_success=out['info'][-1, :, 1].to(torch.int64).cpu().numpy() if out is not None else None,
+                done=out['done'][-1].bool().cpu().numpy() if out is not None else None,
+                loop_s=loop_s, graph_captures=env.sim.graph_captures(), policy_graph=False, fused=True)
+
+
+def evaluate(env_id, actor_critic, ob_rms, n_envs=64, steps=200, deterministic=True, setup=None, device=0, seed=1001, graph=False, fused=False):
     """Run one 200-step trial in each of n_envs envs (enjoy_vr.py:92-116 per env) and return
     per-env episode return, mean total_force_on_human and final task_success, plus the stepping
     loop's wall time (policy forward + env.step, synchronised at both ends) as loop_s.
@@ -132,12 +212,17 @@ def evaluate(env_id, actor_critic, ob_rms, n_envs=64, steps=200, deterministic=T
     graph: replay the policy forward (normalisation + act) as one captured graph (eager if the
     capture fails).  Off by default: measured at 4096 envs it made the loop slower (7.09 vs 6.49
     ms per step, tools/pe_breakdown.py) -- the eager kernels are short, and the copies into the
-    graph's static buffers add to the chain the env step waits on."""
+    graph's static buffers add to the chain the env step waits on.
+    fused: run the policy on the device inside the rollout graphs (_evaluate_fused): the same keys
+    plus fused=True; actions differ from the eager path's in the last bits (another summation
+    order) and, when sampling, in the noise stream."""
     from .env import AVRTorchVecEnv
     env = AVRTorchVecEnv(env_id, n_envs, device=device, seed=seed, auto_reset=False)
     try:
         if setup:
             env.setup(**setup)
+        if fused:
+            return _evaluate_fused(env, actor_critic, ob_rms, steps, deterministic)
         dev = env.dev
         actor_critic = actor_critic.to(dev).eval()
         hxs = torch.zeros(n_envs, actor_critic.recurrent_hidden_state_size, device=dev)

@@ -33,6 +33,12 @@
     int avr_rollout_random_device(avr_sim *s, int64_t t0, int32_t n, float *d_obs, float *d_rew, uint8_t *d_done,   \
                                   float *d_info, int32_t stacked);                                                 \
     int avr_random_actions_device(avr_sim *s, int64_t t, float *d_act);                                            \
+    int avr_policy_set(avr_sim *s, const avr_policy_desc *p);                                                      \
+    int avr_policy_act_device(avr_sim *s, int64_t t, const float *d_obs, int32_t deterministic, float *d_act,       \
+                              float *d_logp, float *d_value);                                                      \
+    int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *d_obs0, int32_t deterministic,    \
+                                  float *d_obs, float *d_act, float *d_logp, float *d_value, float *d_rew,          \
+                                  uint8_t *d_done, float *d_info);                                                 \
     int avr_step(avr_sim *s, const float *act, float *obs, float *rew, uint8_t *done, float *info);                \
     int avr_sync(avr_sim *s);                                                                                      \
     int avr_set_profile_buffer(avr_sim *s, void *d_prof);                                                          \
@@ -182,6 +188,14 @@ int avr_rollout_random_device(avr_sim *s, int64_t t0, int32_t n, float *o, float
     DISPATCH(s, avr_rollout_random_device(h, t0, n, o, r, d, i, stacked));
 }
 int avr_random_actions_device(avr_sim *s, int64_t t, float *a) { DISPATCH(s, avr_random_actions_device(h, t, a)); }
+int avr_policy_set(avr_sim *s, const avr_policy_desc *p) { DISPATCH(s, avr_policy_set(h, p)); }
+int avr_policy_act_device(avr_sim *s, int64_t t, const float *o, int32_t det, float *a, float *lp, float *v) {
+    DISPATCH(s, avr_policy_act_device(h, t, o, det, a, lp, v));
+}
+int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *o0, int32_t det, float *o, float *a, float *lp, float *v, float *r,
+                              uint8_t *d, float *i) {
+    DISPATCH(s, avr_rollout_policy_device(h, t0, n, o0, det, o, a, lp, v, r, d, i));
+}
 int avr_substep(avr_sim *s, float dt) { DISPATCH(s, avr_substep(h, dt)); }
 int avr_sync(avr_sim *s) { DISPATCH(s, avr_sync(h)); }
 int avr_kernel_info(avr_sim *s, int32_t *o) { DISPATCH(s, avr_kernel_info(h, o)); }

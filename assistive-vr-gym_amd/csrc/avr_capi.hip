@@ -70,6 +70,9 @@ struct avr_sim {
     RollSlot rslot[AVR_GRAPH_SLOTS];
     unsigned long long gclock;
     long long n_captures;                  // diagnostics (avr_graph_captures)
+    // the policy on the device (avr_policy_set): the packed weight block (avr_policy.hip), whose
+    // address the rollout graphs' policy nodes hold, and the forward's own log-prob / value rows
+    float *d_pol, *d_logp, *d_val;
 };
 
 // Every entry point runs on the handle's device and restores the caller's current device on
@@ -776,8 +779,29 @@ static bool per_group_rollout(const avr_sim *s) {
     return AVR_TASK == AVR_TASK_FEEDING;
 }
 
-static int rollout_branches(avr_sim *s, int64_t t0, int32_t n, float *o, float *r, uint8_t *dn, float *in, int32_t stacked, const void *const *key) {
-    const size_t E = (size_t)s->cfg.n_envs;
+// a policy rollout's part of a rollout step (avr_rollout_policy_device; nullptr: device-random
+// actions): the forward's flags and the stacked [n][E] outputs it fills beside the handle's rows
+struct PolicyRoll { int flags; float *act, *logp, *value; };
+
+// one step of env group g inside a rollout graph, on the group's stream: the group's counters
+// advance, (policy rollouts) the forward turns the handle's observation rows into its action rows,
+// the step, (stacked) the copy of its outputs to slot k of o / r / dn / in
+static hipError_t roll_step(avr_sim *s, int g, hipStream_t st, float *o, float *r, uint8_t *dn, float *in, int32_t stacked, const PolicyRoll *pr) {
+    const int E = s->cfg.n_envs, e0 = group_bound(s, g), e1 = group_bound(s, g + 1);
+    long long *ct = s->km.step_t + g, *ck = s->km.step_t + AVR_MAX_GROUPS + g;
+    hipError_t el = avr_launch_step_advance(ct, ck, st);
+    if (el == hipSuccess && pr)
+        el = avr_launch_policy(s->d_pol, s->km.step_t, -(g + 1), s->cfg.seed, s->cfg.env_offset, s->d_obs, s->d_act, s->d_logp, s->d_val, pr->act,
+                               pr->logp, pr->value, ck, E, pr->flags, e0, e1, st);
+    if (el == hipSuccess)
+        el = avr_launch_step(&s->km, s->d_km, s->d_state, pr ? s->d_act : nullptr, stacked ? s->d_obs : o, stacked ? s->d_rew : r,
+                             stacked ? s->d_done : dn, stacked ? s->d_info : in, nullptr, pr ? MODE_STEP : MODE_STEP_RANDOM, -(g + 1), e0, e1, st, nullptr);
+    if (el == hipSuccess && stacked) el = avr_launch_rollout_copy(ck, s->d_obs, s->d_rew, s->d_done, s->d_info, o, r, dn, in, e0, e1, E, st);
+    return el;
+}
+
+static int rollout_branches(avr_sim *s, int64_t t0, int32_t n, float *o, float *r, uint8_t *dn, float *in, int32_t stacked, const void *const *key,
+                            const PolicyRoll *pr) {
     avr_sim::RollSlot *rs = nullptr;
     for (auto &x : s->rslot)
         if (x.gexec[0] && memcmp(key, x.key, sizeof(x.key)) == 0) rs = &x;
@@ -797,17 +821,8 @@ static int rollout_branches(avr_sim *s, int64_t t0, int32_t n, float *o, float *
             hipError_t el = hipEventRecord(s->fork_ev, s->stream);
             for (int g = 0; g < s->ngroups && el == hipSuccess; g++) {
                 hipStream_t st = g == 0 ? s->stream : s->gstream[g];
-                const int e0 = group_bound(s, g), e1 = group_bound(s, g + 1);
-                long long *ct = s->km.step_t + g, *ck = s->km.step_t + AVR_MAX_GROUPS + g;
                 if (g > 0) el = hipStreamWaitEvent(st, s->fork_ev, 0);
-                for (int q = 0; q < steps && el == hipSuccess; q++) {
-                    el = avr_launch_step_advance(ct, ck, st);
-                    if (el == hipSuccess)
-                        el = avr_launch_step(&s->km, s->d_km, s->d_state, nullptr, stacked ? s->d_obs : o, stacked ? s->d_rew : r,
-                                             stacked ? s->d_done : dn, stacked ? s->d_info : in, nullptr, 1, -(g + 1), e0, e1, st, nullptr);
-                    if (el == hipSuccess && stacked)
-                        el = avr_launch_rollout_copy(ck, s->d_obs, s->d_rew, s->d_done, s->d_info, o, r, dn, in, e0, e1, (int)E, st);
-                }
+                for (int q = 0; q < steps && el == hipSuccess; q++) el = roll_step(s, g, st, o, r, dn, in, stacked, pr);
                 if (g > 0 && el == hipSuccess) el = hipEventRecord(s->join_ev[g], st);
             }
             for (int g = 1; g < s->ngroups && el == hipSuccess; g++) el = hipStreamWaitEvent(s->stream, s->join_ev[g], 0);
@@ -830,8 +845,8 @@ static int rollout_branches(avr_sim *s, int64_t t0, int32_t n, float *o, float *
 }
 
 
-static int rollout_per_group(avr_sim *s, int64_t t0, int32_t n, float *o, float *r, uint8_t *dn, float *in, int32_t stacked, const void *const *key) {
-    const size_t E = (size_t)s->cfg.n_envs;
+static int rollout_per_group(avr_sim *s, int64_t t0, int32_t n, float *o, float *r, uint8_t *dn, float *in, int32_t stacked, const void *const *key,
+                             const PolicyRoll *pr) {
     avr_sim::RollSlot *rs = nullptr;
     for (auto &x : s->rslot)
         if (x.pgexec[0][0][0] && memcmp(key, x.key, sizeof(x.key)) == 0) rs = &x;
@@ -853,18 +868,9 @@ static int rollout_per_group(avr_sim *s, int64_t t0, int32_t n, float *o, float 
             for (int p = 0; p < 2; p++)
                 for (int g = 0; g < s->ngroups; g++) {
                     hipStream_t st = g == 0 ? s->stream : s->gstream[g];
-                    const int e0 = group_bound(s, g), e1 = group_bound(s, g + 1);
-                    long long *ct = s->km.step_t + g, *ck = s->km.step_t + AVR_MAX_GROUPS + g;
                     HIPCHK(s, hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
                     hipError_t el = hipSuccess;
-                    for (int q = 0; q < (c == 0 ? AVR_ROLL_CHUNK : 1) && el == hipSuccess; q++) {
-                        el = avr_launch_step_advance(ct, ck, st);
-                        if (el == hipSuccess)
-                            el = avr_launch_step(&s->km, s->d_km, s->d_state, nullptr, stacked ? s->d_obs : o, stacked ? s->d_rew : r,
-                                                 stacked ? s->d_done : dn, stacked ? s->d_info : in, nullptr, 1, -(g + 1), e0, e1, st, nullptr);
-                        if (el == hipSuccess && stacked)
-                            el = avr_launch_rollout_copy(ck, s->d_obs, s->d_rew, s->d_done, s->d_info, o, r, dn, in, e0, e1, (int)E, st);
-                    }
+                    for (int q = 0; q < (c == 0 ? AVR_ROLL_CHUNK : 1) && el == hipSuccess; q++) el = roll_step(s, g, st, o, r, dn, in, stacked, pr);
                     hipError_t e = hipStreamEndCapture(st, &rs->pgraph[c][p][g]);
                     if (e == hipSuccess && el == hipSuccess) e = hipGraphInstantiate(&rs->pgexec[c][p][g], rs->pgraph[c][p][g], nullptr, nullptr, 0);
                     if (e != hipSuccess || el != hipSuccess) {
@@ -913,8 +919,113 @@ int avr_rollout_random_device(avr_sim *s, int64_t t0, int32_t n, float *d_obs, f
     // the groups' graphs for these outputs: step outputs straight to the caller's buffers, or
     // (stacked) to the handle's buffers and a copy into slot k
     const void *key[8] = {o, r, dn, in, (const void *)(size_t)(stacked + 1), nullptr, nullptr, nullptr};
-    if (per_group_rollout(s)) return rollout_per_group(s, t0, n, o, r, dn, in, stacked, key);
-    return rollout_branches(s, t0, n, o, r, dn, in, stacked, key);
+    if (per_group_rollout(s)) return rollout_per_group(s, t0, n, o, r, dn, in, stacked, key, nullptr);
+    return rollout_branches(s, t0, n, o, r, dn, in, stacked, key, nullptr);
+}
+
+// ------------------------------------------------------------------ the policy on the device
+int avr_policy_set(avr_sim *s, const avr_policy_desc *p) {
+    CHECK_SIM(s);
+    if (!p) return fail(s, -1, "avr_policy_set: policy is NULL");
+    if (p->n_layers != 2) return fail(s, -1, "avr_policy_set: %d tanh layers per network (exactly 2 are built)", (int)p->n_layers);
+    if (p->hidden < 1 || p->hidden > POL_H) return fail(s, -1, "avr_policy_set: hidden %d outside 1..%d", (int)p->hidden, POL_H);
+    if (p->obs_dim != K_OBS_DIM || p->act_dim != K_ACT_DIM)
+        return fail(s, -1, "avr_policy_set: obs_dim %d / act_dim %d, this task has %d / %d", (int)p->obs_dim, (int)p->act_dim, K_OBS_DIM, K_ACT_DIM);
+    if (!p->a_w1 || !p->a_b1 || !p->a_w2 || !p->a_b2 || !p->mu_w || !p->mu_b || !p->logstd) return fail(s, -1, "avr_policy_set: an actor array is NULL");
+    if (!p->ob_mean != !p->ob_var) return fail(s, -1, "avr_policy_set: ob_mean and ob_var must both be given or both be NULL");
+    const int nc = !!p->c_w1 + !!p->c_b1 + !!p->c_w2 + !!p->c_b2 + !!p->c_w3 + !!p->c_b3;
+    if (nc != 0 && nc != 6) return fail(s, -1, "avr_policy_set: the critic's six arrays must all be given or all be NULL");
+    if (p->ob_mean && !(p->clip_obs > 0.f && p->eps >= 0.f)) return fail(s, -1, "avr_policy_set: clip_obs must be > 0 and eps >= 0");
+    const int H = p->hidden;
+    std::vector<float> w(PW_WORDS, 0.f);
+    w[PW_HDR] = p->ob_mean ? 1.f : 0.f; w[PW_HDR + 1] = nc ? 1.f : 0.f; w[PW_HDR + 2] = p->clip_obs;
+    for (int k = 0; k < 32; k++) w[PW_SD + k] = 1.f;
+    if (p->ob_mean)
+        for (int k = 0; k < K_OBS_DIM; k++) {
+            w[PW_MEAN + k] = p->ob_mean[k];
+            w[PW_SD + k] = (float)std::sqrt((double)p->ob_var[k] + (double)p->eps);
+            if (!(w[PW_SD + k] > 0.f)) return fail(s, -1, "avr_policy_set: ob_var[%d] + eps is not positive", k);
+        }
+    for (int a = 0; a < K_ACT_DIM; a++) {
+        w[PW_LOGSTD + a] = p->logstd[a];
+        w[PW_BH + a] = p->mu_b[a];
+        for (int k = 0; k < H; k++) w[PW_WH + k * 8 + a] = p->mu_w[a * H + k];
+    }
+    if (nc) {
+        w[PW_BH + 7] = p->c_b3[0];
+        for (int k = 0; k < H; k++) w[PW_WH + k * 8 + 7] = p->c_w3[k];
+    }
+    for (int net = 0; net < (nc ? 2 : 1); net++) {
+        float *wn = w.data() + PW_NET + net * PN_WORDS;
+        const float *w1 = net ? p->c_w1 : p->a_w1, *b1 = net ? p->c_b1 : p->a_b1, *w2 = net ? p->c_w2 : p->a_w2, *b2 = net ? p->c_b2 : p->a_b2;
+        for (int j = 0; j < H; j++) {
+            wn[PN_B1 + j] = b1[j]; wn[PN_B2 + j] = b2[j];
+            for (int k = 0; k < K_OBS_DIM; k++) wn[PN_W1 + k * POL_H + j] = w1[j * K_OBS_DIM + k];
+            for (int k = 0; k < H; k++) wn[PN_W2 + k * POL_H + j] = w2[j * H + k];
+        }
+    }
+    if (!s->d_pol) {
+        const size_t E = (size_t)s->cfg.n_envs;
+        float *blk = nullptr;
+        HIPCHK(s, hipMalloc(&blk, (PW_WORDS + 2 * E) * sizeof(float)));
+        s->allocs.push_back(blk);
+        s->d_logp = blk + PW_WORDS; s->d_val = s->d_logp + E;
+        s->d_pol = blk;
+    }
+    // in stream order after every rollout queued so far (each joins its groups back into the
+    // handle's stream); waited for, since the staging vector goes away on return
+    HIPCHK(s, hipMemcpyAsync(s->d_pol, w.data(), PW_WORDS * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+int avr_policy_act_device(avr_sim *s, int64_t t, const float *d_obs, int32_t deterministic, float *d_act, float *d_logp, float *d_value) {
+    CHECK_SIM(s);
+    if (!s->d_pol) return fail(s, -1, "avr_policy_act_device: no policy (call avr_policy_set first)");
+    if (t < 0) return fail(s, -1, "avr_policy_act_device: step index %lld < 0", (long long)t);
+    if (!d_obs || (!d_act && !d_value)) return fail(s, -1, "avr_policy_act_device: d_obs and one of d_act, d_value must be given");
+    const int E = s->cfg.n_envs;
+    HIPCHK(s, avr_launch_policy(s->d_pol, s->km.step_t, t, s->cfg.seed, s->cfg.env_offset, d_obs, d_act, d_act ? d_logp : nullptr, d_value, nullptr,
+                                nullptr, nullptr, nullptr, E, (deterministic ? POL_DETERMINISTIC : 0) | (d_act ? 0 : POL_VALUE_ONLY), 0, E, s->stream));
+    return 0;
+}
+
+int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *d_obs0, int32_t deterministic, float *d_obs, float *d_act, float *d_logp,
+                              float *d_value, float *d_rew, uint8_t *d_done, float *d_info) {
+    CHECK_SIM(s);
+    if (!s->d_pol) return fail(s, -1, "avr_rollout_policy_device: no policy (call avr_policy_set first)");
+    if (t0 < 0 || n < 0) return fail(s, -1, "avr_rollout_policy_device: t0 %lld / n %d < 0", (long long)t0, n);
+    if (!(d_obs && d_act && d_rew && d_done && d_info)) return fail(s, -1, "avr_rollout_policy_device: d_obs, d_act, d_rew, d_done and d_info must be given");
+    const size_t E = (size_t)s->cfg.n_envs, OB = E * K_OBS_DIM;
+    const int flags = deterministic ? POL_DETERMINISTIC : 0;
+    if (d_obs0 && d_obs0 != s->d_obs) HIPCHK(s, hipMemcpyAsync(s->d_obs, d_obs0, OB * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    HIPCHK(s, hipMemcpyAsync(d_obs, s->d_obs, OB * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    if (n > 0 && (!s->use_graph || s->ngroups <= 1 || s->evlog.cap)) {
+        // the direct loop: each step's outputs land in the handle's buffers (one step graph, or
+        // direct launches) and are copied to their slots in stream order
+        for (size_t k = 0; k < (size_t)n; k++) {
+            HIPCHK(s, avr_launch_policy(s->d_pol, s->km.step_t, t0 + (int64_t)k, s->cfg.seed, s->cfg.env_offset, s->d_obs, s->d_act, s->d_logp, s->d_val,
+                                        d_act + k * E * K_ACT_DIM, d_logp ? d_logp + k * E : nullptr, d_value ? d_value + k * E : nullptr, nullptr,
+                                        (int)E, flags, 0, (int)E, s->stream));
+            HIPCHK(s, run_step(s, s->d_state, s->d_act, s->d_obs, s->d_rew, s->d_done, s->d_info, nullptr, 0, 0));
+            HIPCHK(s, hipMemcpyAsync(d_obs + (k + 1) * OB, s->d_obs, OB * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+            HIPCHK(s, hipMemcpyAsync(d_rew + k * E, s->d_rew, E * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+            HIPCHK(s, hipMemcpyAsync(d_done + k * E, s->d_done, E, hipMemcpyDeviceToDevice, s->stream));
+            HIPCHK(s, hipMemcpyAsync(d_info + k * E * AVR_INFO_DIM, s->d_info, E * AVR_INFO_DIM * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+        }
+    } else if (n > 0) {
+        // the random rollout's graphs with the forward in front of every step; the step's
+        // observation goes to slot k + 1, hence the stacked observation array shifted by one slot
+        const PolicyRoll pr = {flags, d_act, d_logp, d_value};
+        const void *key[8] = {d_obs, d_rew, d_done, d_info, (const void *)(size_t)(3 + flags), d_act, d_logp, d_value};
+        const int rc = per_group_rollout(s) ? rollout_per_group(s, t0, n, d_obs + OB, d_rew, d_done, d_info, 1, key, &pr)
+                                            : rollout_branches(s, t0, n, d_obs + OB, d_rew, d_done, d_info, 1, key, &pr);
+        if (rc) return rc;
+    }
+    if (d_value)       // the bootstrap value of the final observation (the groups are joined by now)
+        HIPCHK(s, avr_launch_policy(s->d_pol, s->km.step_t, t0 + n, s->cfg.seed, s->cfg.env_offset, s->d_obs, nullptr, nullptr, s->d_val, nullptr, nullptr,
+                                    d_value + (size_t)n * E, nullptr, (int)E, POL_VALUE_ONLY, 0, (int)E, s->stream));
+    return 0;
 }
 
 int avr_random_actions_device(avr_sim *s, int64_t t, float *d_act) {

@@ -864,6 +864,18 @@ int avr_random_actions_device(avr_sim *s, int64_t t, float *d_act) {
     HIPCHK(s, hipGetLastError());
     return 0;
 }
+// (the policy on the device runs between the steps of the multi-kernel tasks' rollout graphs,
+// avr_policy.hip / avr_capi.hip; this task's single-kernel step is not wired to it)
+int avr_policy_set(avr_sim *s, const avr_policy_desc *p) { (void)p; return fail(s, -1, "policy rollouts: not built for DressingJaco"); }
+int avr_policy_act_device(avr_sim *s, int64_t t, const float *d_obs, int32_t deterministic, float *d_act, float *d_logp, float *d_value) {
+    (void)t; (void)d_obs; (void)deterministic; (void)d_act; (void)d_logp; (void)d_value;
+    return fail(s, -1, "policy rollouts: not built for DressingJaco");
+}
+int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *d_obs0, int32_t deterministic, float *d_obs, float *d_act, float *d_logp,
+                              float *d_value, float *d_rew, uint8_t *d_done, float *d_info) {
+    (void)t0; (void)n; (void)d_obs0; (void)deterministic; (void)d_obs; (void)d_act; (void)d_logp; (void)d_value; (void)d_rew; (void)d_done; (void)d_info;
+    return fail(s, -1, "policy rollouts: not built for DressingJaco");
+}
 int avr_step(avr_sim *s, const float *act, float *obs, float *rew, uint8_t *done, float *info) {
     CHECK_SIM(s);
     const size_t E = (size_t)s->cfg.n_envs;

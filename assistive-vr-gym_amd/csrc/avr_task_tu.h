@@ -24,5 +24,6 @@ namespace AVR_NS {
 #include "avr_kernel.hip"
 #include "avr_reset_ik.hip"
 #include "avr_base_search.hip"
+#include "avr_policy.hip"
 #include "avr_capi.hip"
 }  // namespace AVR_NS

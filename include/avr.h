@@ -36,7 +36,10 @@ extern "C" {
 #define AVR_ABI_VERSION 6      /* 3: task-selected layouts (avr_model_desc.task), 5-kernel info, state getters;
                                   4: BedBathingPR2 (avr_model_desc bb_* fields, task 2);
                                   5: avr_graph_captures, per-handle device guard, t >= 0;
-                                  6: avr_reset_ik self-contact screening (alt4), avr_robot_self_contact */
+                                  6: avr_reset_ik self-contact screening (alt4), avr_robot_self_contact;
+                                  still 6: avr_policy_set, avr_policy_act_device, avr_rollout_policy_device are new
+                                  exports only -- no existing signature or state layout changed, so recordings
+                                  (avr/record.py refuses another ABI number) stay valid */
 #define AVR_FLAGS_FAULT_MASK 0x1f  /* avr_get_flags bits 0-4; bit 5 (EPA budget) is informational */
 
 typedef struct avr_config {
@@ -102,6 +105,50 @@ int avr_step_random_device(avr_sim *sim, int64_t t, float *d_obs, float *d_rew, 
 int avr_rollout_random_device(avr_sim *sim, int64_t t0, int32_t n, float *d_obs, float *d_rew, uint8_t *d_done, float *d_info, int32_t stacked);
 /* Device actions for inspection: d_act[n_envs*7] for step t (same Philox stream). */
 int avr_random_actions_device(avr_sim *sim, int64_t t, float *d_act);
+
+/* ---- the policy on the device (FeedingJaco, ScratchItchPR2, BedBathingPR2; DressingJaco: -1) ----
+ * An MLP actor-critic with two tanh layers of `hidden` <= 64 units per network (the harness's
+ * ActorCritic, avr/policy_eval.py: what enjoy_vr.py:80 loads and :103 calls), with VecNormalize's
+ * eval-mode normalisation (enjoy_vr.py:85-88) in front:
+ *   x = clip((obs - ob_mean) / sqrt(ob_var + eps), -clip_obs, clip_obs)     (ob_mean, ob_var both NULL: x = obs)
+ *   mean = mu_w tanh(a_w2 tanh(a_w1 x + a_b1) + a_b2) + mu_b,  std = exp(logstd)
+ *   action = mean (deterministic) or mean + std eps;  logp = sum_a -eps_a^2 / 2 - logstd_a - log(2 pi) / 2
+ *   value = c_w3 tanh(c_w2 tanh(c_w1 x + c_b1) + c_b2) + c_b3                (the six c_* all NULL: value = 0)
+ * eps[e][a] at step t is a Box-Muller normal from Philox4x32-10 keyed by (seed, env_offset + e, t)
+ * on counters the action stream of avr_step_random_device never uses (avr/_lib.py policy_noise is
+ * the host mirror).  Host pointers; matrices row-major [out][in] as torch.nn.Linear.weight. */
+typedef struct avr_policy_desc {
+    int32_t obs_dim, act_dim;     /* must equal the handle's task's (25 / 30 / 24, 7)                  */
+    int32_t hidden;               /* 1 .. 64                                                          */
+    int32_t n_layers;             /* tanh layers per network: must be 2                               */
+    float clip_obs, eps;          /* VecNormalize clipob (10), epsilon (1e-8)                         */
+    const float *ob_mean, *ob_var;                        /* [obs_dim]                                */
+    const float *a_w1, *a_b1, *a_w2, *a_b2;               /* [hidden][obs_dim], [hidden], [hidden][hidden], [hidden] */
+    const float *mu_w, *mu_b, *logstd;                    /* [act_dim][hidden], [act_dim], [act_dim]  */
+    const float *c_w1, *c_b1, *c_w2, *c_b2, *c_w3, *c_b3; /* as the actor's, then [1][hidden], [1]    */
+} avr_policy_desc;
+/* Validate the descriptor and pack it into the handle's device weight block (allocated by the
+ * first call, overwritten in stream order by later ones: the block's address never changes, so a
+ * new set of weights -- a PPO update between rollouts -- needs no graph re-capture). */
+int avr_policy_set(avr_sim *sim, const avr_policy_desc *policy);
+/* One forward over all envs at step index t >= 0 (it keys the noise): d_obs[n_envs*obs_dim] ->
+ * d_act[n_envs*act_dim], d_logp[n_envs], d_value[n_envs] (d_logp, d_value may be NULL; d_act NULL:
+ * the value alone).  Asynchronous on avr_stream(sim).  An error before avr_policy_set. */
+int avr_policy_act_device(avr_sim *sim, int64_t t, const float *d_obs, int32_t deterministic, float *d_act, float *d_logp, float *d_value);
+/* n steps t0 .. t0+n-1 with the policy in the loop, bit-identical to n x {avr_policy_act_device(t0 + k,
+ * obs_k); avr_step_device(act_k)}, with no host work per step: the forward runs between the steps
+ * inside the rollout graphs of avr_rollout_random_device (per env group, joined every 16 steps).
+ * d_obs0[n_envs*obs_dim] is the observation step t0's policy sees (NULL: the handle's own
+ * observation buffer, as avr_reset / avr_settle / an earlier rollout left it); it is first copied
+ * in stream order into that buffer.  Outputs are stacked:
+ *   d_obs[n+1][n_envs][obs_dim]   slot 0 = obs0, slot k+1 = the observation after step k
+ *   d_act[n][n_envs][act_dim], d_logp[n][n_envs], d_rew[n][n_envs], d_done[n][n_envs],
+ *   d_info[n][n_envs][AVR_INFO_DIM]                                    one slot per step
+ *   d_value[n+1][n_envs]          slot k = V(obs slot k) (the last by one value-only launch)
+ * d_logp and d_value may be NULL.  No reset inside a rollout: done comes out and the caller resets
+ * (as avr_rollout_random_device).  An error before avr_policy_set. */
+int avr_rollout_policy_device(avr_sim *sim, int64_t t0, int32_t n, const float *d_obs0, int32_t deterministic, float *d_obs, float *d_act,
+                              float *d_logp, float *d_value, float *d_rew, uint8_t *d_done, float *d_info);
 
 /* One Bullet sub-step of length dt for every env, no task glue (known-answer tests). */
 int avr_substep(avr_sim *sim, float dt);
