@@ -20,7 +20,7 @@ EXPORTS = [
     'avr_kernel_info', 'avr_last_error', 'avr_substep', 'avr_reset', 'avr_profile_kernels', 'avr_kernel_times',
     'avr_hull_support_table', 'avr_task', 'avr_task_state_words', 'avr_task_obs_dim', 'avr_task_act_dim', 'avr_n_dof',
     'avr_get_q', 'avr_get_link_pose', 'avr_get_contact_summary', 'avr_get_flags', 'avr_reset_ik', 'avr_base_search',
-    'avr_graph_captures', 'avr_robot_self_contact', 'avr_narrowphase_query',
+    'avr_graph_captures', 'avr_robot_self_contact', 'avr_narrowphase_query', 'avr_bb_closest_query',
     'avr_policy_set', 'avr_policy_act_device', 'avr_rollout_policy_device',
 ]
 FLAGS_FAULT_MASK = 0x1f      # include/avr.h AVR_FLAGS_FAULT_MASK: bits 0-4; bit 5 (EPA budget) is informational
@@ -107,6 +107,8 @@ def load(path=LIB_PATH):
     lib.avr_reset_ik.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp, C.c_int32, vp, vp]
     lib.avr_robot_self_contact.argtypes = [vp, C.c_int32, vp, vp]
     lib.avr_narrowphase_query.argtypes = [vp, C.c_int32, vp, vp, C.c_float, vp]
+    if hasattr(lib, 'avr_bb_closest_query'):        # (absent in experiment builds of older trees)
+        lib.avr_bb_closest_query.argtypes = [vp, C.c_int32, vp]
     lib.avr_base_search.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_float, vp, vp, vp, vp]
     if lib.avr_abi_version() != ABI.ABI_VERSION or any(
             lib.avr_task_state_words(t) != L.STATE_WORDS or lib.avr_task_obs_dim(t) != L.OBS_DIM or lib.avr_task_act_dim(t) != L.ACT_DIM
@@ -231,6 +233,15 @@ class Sim:
         x = np.ascontiguousarray(poses14, np.float32).reshape(len(p), 14)
         out = np.zeros((len(p), 8), np.float32)
         self._chk(self.lib.avr_narrowphase_query(self.h, int(len(p)), p.ctypes.data, x.ctypes.data, float(thr), out.ctypes.data))
+        return out
+
+    def bb_closest_query(self, cap=-1):
+        """BedBathing's closest tool-human distance of every env's current state, by the step's code
+        (include/avr.h avr_bb_closest_query): (n_envs, 4) {final minimum, queued stalled pairs,
+        minimum before their rerun, stalled pairs past the queue's capacity}.  cap: the queue's
+        capacity for this call (negative: the step's)."""
+        out = np.zeros((self.n, 4), np.float32)
+        self._chk(self.lib.avr_bb_closest_query(self.h, int(cap), out.ctypes.data))
         return out
 
     def base_search(self, base7, rest, tstart, goals, iters=200, tol=0.03, per_attempt=False):

@@ -1262,6 +1262,25 @@ int avr_narrowphase_query(avr_sim *s, int32_t n, const int32_t *pairs, const flo
     return 0;
 }
 
+// ------------------------------------------------------------------ BedBathing closest-distance query (test hook)
+int avr_bb_closest_query(avr_sim *s, int32_t cap, float *out4) {
+    CHECK_SIM(s);
+#if AVR_TASK != AVR_TASK_BEDBATH
+    (void)cap; (void)out4;
+    return fail(s, -1, "avr_bb_closest_query: BedBathingPR2's closest-distance query (this task has none)");
+#else
+    if (!out4) return fail(s, -1, "avr_bb_closest_query: out4 must be given");
+    if (cap > WS_BB_CAP) return fail(s, -1, "avr_bb_closest_query: cap %d above the queue's %d words", (int)cap, (int)WS_BB_CAP);
+    const size_t E = (size_t)s->cfg.n_envs;
+    float *d = nullptr;
+    if (query_buf(s, 4 * E, &d)) return -3;
+    HIPCHK(s, avr_launch_bb_query(s->d_km, s->d_state, d, cap < 0 ? WS_BB_CAP : (int)cap, (int)E, s->stream));
+    HIPCHK(s, hipMemcpyAsync(out4, d, 4 * E * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    return 0;
+#endif
+}
+
 // ------------------------------------------------------------------ device base-pose search (PR2 tasks)
 int avr_base_search(avr_sim *s, int32_t n, int32_t attempts, const float *base7, const float *rest, const float *tstart3, const float *goals9,
                     int32_t iters, float tol, int32_t *best, uint8_t *ok, float *q_arm, float *res4) {

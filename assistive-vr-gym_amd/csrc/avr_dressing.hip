@@ -944,6 +944,10 @@ int avr_narrowphase_query(avr_sim *s, int32_t n, const int32_t *pairs, const flo
     (void)n; (void)pairs; (void)poses14; (void)thr; (void)out8;
     return fail(s, -1, "avr_narrowphase_query: DressingJaco has no rigid collision model");
 }
+int avr_bb_closest_query(avr_sim *s, int32_t cap, float *out4) {
+    (void)cap; (void)out4;
+    return fail(s, -1, "avr_bb_closest_query: BedBathingPR2's closest-distance query (this task has none)");
+}
 int avr_robot_self_contact(avr_sim *s, int32_t n, const float *q, int32_t *out) {
     (void)n; (void)q; (void)out;
     return fail(s, -1, "avr_robot_self_contact: DressingJaco's robot is kinematic (no robot collision model)");

@@ -117,19 +117,25 @@ AVR_DI BBForces bb_forces(const KModel &m, EnvLDS &L, BBShared &B, const float *
 // wave-cooperative path (EPA) for the penetrating pairs it hands on.  A lane GJK that stalls with
 // an open duality gap (rc 4) is queued in the env's workspace (WS_BB_*) for avr_bb_stall_kernel,
 // which reruns it with the double simplex solve (gjk_coop_d, as the step's narrowphase does) and
-// finishes the reward: the double code here would take this kernel from 211 to 256 VGPRs.  Pairs
-// past the queue's capacity rerun on the fp32 cooperative GJK.  Poses: the state after the step
-// (the tool's body frame, the human slots).
-#define WS_BB_N 64          // int bits: queued stalled pairs
+// finishes the reward: the double code here would take this kernel from 211 to 256 VGPRs.
+// Stalled pairs past the queue's capacity are counted only (novf): the stall kernel finds them
+// again with the same lane GJK (OVF: this function's second mode, which runs the lane GJK of every
+// pair, skips the first `cap` stalled pairs -- the queue's -- and returns the minimum over the
+// others' double reruns).  Poses: the state after the step (st: the tool's body frame, the human
+// slots).  `cap` is the queue's capacity, WS_BB_CAP in the step (a constant there: the call is
+// inlined); avr_bb_closest_query (test hook) passes a smaller one to reach the path past it.
+#define WS_BB_N 64          // int bits: stalled pairs (the first WS_BB_CAP of them are queued)
 #define WS_BB_DMIN 65       // the minimum over the other pairs (BIGF: none within reach)
 #define WS_BB_WIPED 66      // the step's wiped-target count
 #define WS_BB_PREFS 67      // the human-preference terms
 #define WS_BB_PAIRS 68      // int bits: sa | sb << 16 of each queued pair
 #define WS_BB_CAP (WS_WORDS - WS_BB_PAIRS)
 static_assert(WS_FW + 4 * MAXF <= WS_BB_N, "the stalled-pair queue lies past the velocity words");
-AVR_DI float bb_closest(const KModel &m, const EnvLDS &L, EpaBuf &E, float *ws, int &nq) {
+struct BBView { const float *st; int gender; };
+template <bool OVF = false, class LT>
+AVR_DI float bb_closest(const KModel &m, const LT &L, EpaBuf &E, float *ws, int &ns, const int cap = WS_BB_CAP) {
     const int lane = lane_id();
-    nq = 0;
+    ns = 0;          // stalled pairs so far
     const int tb = m.tool_body, ts0 = gld(m.body_shape_start + tb), nts = gld(m.body_shape_count + tb);
     int hs0 = 1 << 30, hs1 = 0;
     for (int b = 0; b < m.nb; b++)
@@ -154,26 +160,26 @@ AVR_DI float bb_closest(const KModel &m, const EnvLDS &L, EpaBuf &E, float *ws, 
         if (sa >= 0) {
             const int bb = gld(m.shape_body + sb);
             const WShape A = make_wshape(m, sa, ttf), Bs = make_wshape(m, sb, ldtf(L.st + S_HUMAN + 7 * gld(m.body_index + bb)));
-            if ((A.nv > SMALL_NV && A.tab < 0) || (Bs.nv > SMALL_NV && Bs.tab < 0)) coop = true;
+            if ((A.nv > SMALL_NV && A.tab < 0) || (Bs.nv > SMALL_NV && Bs.tab < 0)) coop = !OVF;
             else {
                 v3 nB = V(0, 0, 0), pB = V(0, 0, 0);
                 float d = 0.f;
                 int nit, nk;
                 const int rc = narrowphase<false>(m, E, A, Bs, thr, nB, pB, d, nit, nk);
-                if (rc == 1) dmin = fminf(dmin, d);
+                if (rc == 1) dmin = OVF ? dmin : fminf(dmin, d);
                 else if (rc == 4) stall = true;
-                else if (rc == 2) coop = true;
+                else if (rc == 2) coop = !OVF;
             }
         }
-        // stalled pairs into the queue, in order; past its capacity onto the fp32 cooperative path
+        // stalled pairs into the queue, in order; past its capacity counted (OVF: rerun in double)
         {
             int tot;
             const int pre = ballot_prefix(stall, &tot);
             if (stall) {
-                if (nq + pre < WS_BB_CAP) ws[WS_BB_PAIRS + nq + pre] = __int_as_float(sa | sb << 16);
-                else coop = true;
+                if (ns + pre >= cap) coop = OVF;
+                else if (!OVF) ws[WS_BB_PAIRS + ns + pre] = __int_as_float(sa | sb << 16);
             }
-            nq = min(nq + tot, WS_BB_CAP);
+            ns += tot;
         }
         unsigned long long cm = __ballot(coop);
         while (cm) {
@@ -185,7 +191,7 @@ AVR_DI float bb_closest(const KModel &m, const EnvLDS &L, EpaBuf &E, float *ws, 
             v3 nB = V(0, 0, 0), pB = V(0, 0, 0);
             float d = 0.f;
             int nit, nk;
-            const int rc = narrowphase<true>(m, E, A, Bs, thr, nB, pB, d, nit, nk);
+            const int rc = narrowphase<true>(m, E, A, Bs, thr, nB, pB, d, nit, nk, nullptr, OVF);
             SYNC();
             if (lane == 0 && rc == 1) dmin = fminf(dmin, d);
         }
@@ -263,20 +269,13 @@ __global__ __launch_bounds__(64) void avr_task_kernel(const KModel *__restrict__
     prof_flush(m, L, env);
 }
 
-// The closest-distance pairs whose lane GJK stalled (bb_closest's queue), rerun with the
-// cooperative GJK's double simplex solve -- the step narrowphase's treatment of the same stop --
-// and the reward finished from the full minimum (bb_reward).  One wave per env; an env with an
-// empty queue (nearly all) returns at once.
-__global__ __launch_bounds__(64) void avr_bb_stall_kernel(const KModel *__restrict__ mp, float *__restrict__ state, float *__restrict__ rew,
-                                                          const unsigned char *__restrict__ mask, int env0, int n_envs) {
-    __shared__ EpaBuf E;
-    const int env = env0 + blockIdx.x;
-    if (env >= n_envs || (mask && !mask[env])) return;
-    const KModel &m = *mp;
-    float *ws = env_ws(m, env);
-    const int nq = __float_as_int(ws[WS_BB_N]);
-    if (nq <= 0) return;
-    const float *gst = state + (size_t)env * K_STATE_WORDS;
+// The closest-distance pairs whose lane GJK stalled (bb_closest's queue of nq pairs), rerun with
+// the cooperative GJK's double simplex solve -- the step narrowphase's treatment of the same stop:
+// the minimum over them and the other pairs' minimum (WS_BB_DMIN).  ns: the env's stalled pairs
+// (WS_BB_N); with more of them than the queue's capacity the lane GJK of every pair runs again to
+// find the others (bb_closest<true>).  Wave-cooperative.
+AVR_DI float bb_stall_min(const KModel &m, EpaBuf &E, const float *gst, float *ws, int ns, const int cap = WS_BB_CAP) {
+    const int nq = min(ns, cap);
     const tf ttf = ldtf(gst + S_FREE);
     const float thr = m.closest_distance;
     float dmin = ws[WS_BB_DMIN];
@@ -292,5 +291,69 @@ __global__ __launch_bounds__(64) void avr_bb_stall_kernel(const KModel *__restri
         SYNC();
         if (rc == 1) dmin = fminf(dmin, d);
     }
+    if (ns > cap) {
+        int n2;
+        dmin = fminf(dmin, bb_closest<true>(m, BBView{gst, (int)gst[S_TASK + T_GENDER]}, E, ws, n2, cap));
+    }
+    return dmin;
+}
+
+// The step's stalled pairs: the reward finished from the full minimum (bb_reward).  One wave per
+// env; an env with an empty queue (nearly all) returns at once.
+__global__ __launch_bounds__(64) void avr_bb_stall_kernel(const KModel *__restrict__ mp, float *__restrict__ state, float *__restrict__ rew,
+                                                          const unsigned char *__restrict__ mask, int env0, int n_envs) {
+    __shared__ EpaBuf E;
+    const int env = env0 + blockIdx.x;
+    if (env >= n_envs || (mask && !mask[env])) return;
+    const KModel &m = *mp;
+    float *ws = env_ws(m, env);
+    const int ns = __float_as_int(ws[WS_BB_N]);
+    if (ns <= 0) return;
+    const float dmin = bb_stall_min(m, E, state + (size_t)env * K_STATE_WORDS, ws, ns);
     if (lane_id() == 0) rew[env] = bb_reward(m, dmin, ws[WS_ASQ], ws[WS_BB_WIPED], ws[WS_BB_PREFS]);
+}
+
+// avr_bb_closest_query (test hook): the step's closest-distance query on the handle's current
+// state, in the step's two parts -- bb_closest (the lane and cooperative pairs, the queue in the
+// env's workspace, at most `cap` pairs long) in a kernel of its own, then the queue's rerun.
+// out[4 env ..] = {final minimum, queued pairs, the minimum before the rerun, stalled pairs past
+// the capacity}, "none within reach" as closest_distance (bb_reward's reading).  Reads the state;
+// writes the env's WS_BB_N, WS_BB_DMIN and queue words, which every step rewrites before use.
+__global__ __launch_bounds__(64) void avr_bb_query_lane_kernel(const KModel *__restrict__ mp, const float *__restrict__ state, float *__restrict__ out,
+                                                               int cap, int n_envs) {
+    __shared__ EnvLDS L;
+    __shared__ EpaBuf E;
+    const int env = blockIdx.x;
+    if (env >= n_envs) return;
+    const KModel &m = *mp;
+    load_state(m, L, state + (size_t)env * K_STATE_WORDS);
+    float *ws = env_ws(m, env);
+    int ns;
+    const float dmin = bb_closest(m, L, E, ws, ns, cap);
+    SYNC();
+    if (lane_id() == 0) {
+        ws[WS_BB_N] = __int_as_float(ns);
+        ws[WS_BB_DMIN] = dmin;
+        float *o = out + 4 * (size_t)env;
+        o[1] = (float)min(ns, cap);
+        o[2] = dmin < BIGF ? dmin : m.closest_distance;
+        o[3] = (float)(ns - min(ns, cap));
+    }
+}
+__global__ __launch_bounds__(64) void avr_bb_query_stall_kernel(const KModel *__restrict__ mp, const float *__restrict__ state, float *__restrict__ out,
+                                                                int cap, int n_envs) {
+    __shared__ EpaBuf E;
+    const int env = blockIdx.x;
+    if (env >= n_envs) return;
+    const KModel &m = *mp;
+    float *ws = env_ws(m, env);
+    const float dmin = bb_stall_min(m, E, state + (size_t)env * K_STATE_WORDS, ws, __float_as_int(ws[WS_BB_N]), cap);
+    if (lane_id() == 0) out[4 * (size_t)env] = dmin < BIGF ? dmin : m.closest_distance;
+}
+hipError_t avr_launch_bb_query(const KModel *d_m, const float *state, float *out, int cap, int n_envs, hipStream_t st) {
+    if (n_envs <= 0) return hipSuccess;
+    cap = min(max(cap, 0), (int)WS_BB_CAP);
+    hipLaunchKernelGGL(avr_bb_query_lane_kernel, dim3(n_envs), dim3(64), 0, st, d_m, state, out, cap, n_envs);
+    hipLaunchKernelGGL(avr_bb_query_stall_kernel, dim3(n_envs), dim3(64), 0, st, d_m, state, out, cap, n_envs);
+    return hipGetLastError();
 }

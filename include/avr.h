@@ -251,6 +251,20 @@ int avr_robot_self_contact(avr_sim *sim, int32_t n, const float *q, int32_t *out
  *   cooperative GJK with the double simplex solve, every other pair by the cooperative fp32 path. */
 int avr_narrowphase_query(avr_sim *sim, int32_t n, const int32_t *pairs, const float *poses14, float thr, float *out8);
 
+/* avr_bb_closest_query (test hook, BedBathingPR2): min p.getClosestPoints(tool, human, 4.0)[8]
+ *   (bed_bathing.py:61) of every env's current state, computed by the step's own code in the
+ *   step's two parts: the lane and wave-cooperative narrowphase over the tool x human shape pairs,
+ *   which queues the pairs whose fp32 lane GJK stalls with an open duality gap in the env's
+ *   workspace, then the queue's rerun with the double simplex solve.  The counterpart of the
+ *   oracle's avr_oracle_bb_closest; no step is taken, and state, observation and reward buffers are
+ *   not touched.  out4[4e..] = {the final minimum, the number of queued pairs, the minimum before
+ *   the rerun (the lane and cooperative pairs only), the number of stalled pairs past the queue's
+ *   capacity (the rerun finds them again with the lane GJK and gives them the double solve as
+ *   well)}; "no pair within reach" reads as the query
+ *   distance 4.0, as in the reward.  cap limits the queue for this call: 0 <= cap <= the step's
+ *   capacity (60), negative = the step's.  Returns -1 for the other tasks. */
+int avr_bb_closest_query(avr_sim *sim, int32_t cap, float *out4);
+
 /* ---- device base-pose search (ScratchItchPR2, BedBathingPR2) ----
  * avr_base_search: position_robot_toc (env.py:489-585; scratch_itch.py:189-190,
  *   bed_bathing.py:317) for n envs on the device, one lane per (env, attempt).  Host buffers:

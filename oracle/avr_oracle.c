@@ -581,28 +581,29 @@ static int simplex_closest(simplex *S, v3 *vout, real lam[4]) {
     /* tetrahedron: test the faces that can see the origin */
     static const int F[4][4] = {{0, 1, 2, 3}, {0, 3, 1, 2}, {0, 2, 3, 1}, {1, 3, 2, 0}};
     real best = BT_LARGE;
-    simplex bestS;
+    simplex bestS = *S;
     real bestL[4] = {0, 0, 0, 0};
     v3 bestv = V(0, 0, 0);
-    int outside_any = 0;
+    int chosen = 0;
     for (int f = 0; f < 4; f++) {
         v3 A = S->w[F[f][0]], B = S->w[F[f][1]], C = S->w[F[f][2]], D = S->w[F[f][3]];
         v3 n = crs(sub(B, A), sub(C, A));
         real sp = dot(scl(A, -1), n), sd = dot(sub(D, A), n);
         if (sd * sd < 1e-30) continue;          /* degenerate tetra face */
         if (sp * sd < 0) {                      /* origin and D on opposite sides */
-            outside_any = 1;
             simplex T;
             for (int k = 0; k < 3; k++) { T.w[k] = S->w[F[f][k]]; T.a[k] = S->a[F[f][k]]; T.b[k] = S->b[F[f][k]]; }
             T.n = 3;
-            real L[4];
+            real L[4] = {0, 0, 0, 0};
             v3 v;
             simplex_closest(&T, &v, L);
             real d2 = len2(v);
-            if (d2 < best) { best = d2; bestS = T; bestv = v; for (int k = 0; k < 4; k++) bestL[k] = L[k]; }
+            if (isfinite(d2) && d2 < best) { chosen = 1; best = d2; bestS = T; bestv = v; for (int k = 0; k < 4; k++) bestL[k] = L[k]; }
         }
     }
-    if (!outside_any) { lam[0] = lam[1] = lam[2] = lam[3] = 0; *vout = V(0, 0, 0); return 1; }
+    /* no face chosen: the origin is inside, or every outside face's distance is NaN / inf (no
+     * usable face) -- penetrating, as the kernel's simplex_closest_d answers */
+    if (!chosen) { lam[0] = lam[1] = lam[2] = lam[3] = 0; *vout = V(0, 0, 0); return 1; }
     *S = bestS;
     for (int k = 0; k < 4; k++) lam[k] = bestL[k];
     *vout = bestv;
@@ -705,7 +706,7 @@ static int simplex_closest_dbl(simplex *S, v3 *vout, real lam[4]) {
         double la, lb, lc;
         d3_t cv = tri_cp_dbl(A, B, C, &used, &la, &lb, &lc);
         real d2 = (real)ddot(cv, cv);
-        if (bf < 0 || d2 < best) { best = d2; bf = f; bused = used; bla = la; blb = lb; blc = lc; bcv = cv; }
+        if (isfinite(d2) && d2 < best) { best = d2; bf = f; bused = used; bla = la; blb = lb; blc = lc; bcv = cv; }
     }
     if (bf < 0) { lam[0] = lam[1] = lam[2] = lam[3] = 0; *vout = V(0, 0, 0); return 1; }
     simplex T = *S;
@@ -2042,6 +2043,29 @@ EXPORT void avr_oracle_set_threads(avr_oracle *o, int n) { o->threads = n > 0 ? 
 /* test-only: the PGS residual exit per island instead of per env (solve_islands) */
 EXPORT void avr_oracle_set_island_exit(avr_oracle *o, int on) {
     for (int e = 0; e < o->n_envs; e++) o->ws[e].island_exit = on;
+}
+
+/* test-only: the narrowphase without the lane GJK's stall rule (narrowphase(): np_plain), to show
+ * what the rule repairs; the shipped paths leave it unset */
+EXPORT void avr_oracle_set_np_plain(avr_oracle *o, int on) {
+    for (int e = 0; e < o->n_envs; e++) o->ws[e].np_plain = on;
+}
+
+/* test-only: the GJK's closest-point solve on a simplex of n vertices w[3n] (the support points on
+ * A and B are not tracked): dbl selects simplex_closest_dbl.  out8 = {vertices kept, closest point
+ * xyz, weights[4]}; returns the solve's answer (1: the origin is inside / no usable face) */
+EXPORT int avr_oracle_simplex_closest(const double *w, int n, int dbl, double *out8) {
+    simplex S;
+    memset(&S, 0, sizeof(S));
+    if (n < 1 || n > 4) return -1;
+    for (int k = 0; k < n; k++) S.w[k] = V(R(w[3 * k]), R(w[3 * k + 1]), R(w[3 * k + 2]));
+    S.n = n;
+    v3 v = V(0, 0, 0);
+    real lam[4] = {0, 0, 0, 0};
+    int r = dbl ? simplex_closest_dbl(&S, &v, lam) : simplex_closest(&S, &v, lam);
+    out8[0] = S.n; out8[1] = v.x; out8[2] = v.y; out8[3] = v.z;
+    for (int k = 0; k < 4; k++) out8[4 + k] = lam[k];
+    return r;
 }
 
 /* geometry query for tests: narrowphase between shapes sa (on body pose pa[7]) and sb (pb[7]) */

@@ -40,6 +40,8 @@ def _load(precision, task=0):
     lib.avr_oracle_substep.argtypes = [vp, C.c_double]
     lib.avr_oracle_stats.argtypes = [vp, vp]
     lib.avr_oracle_set_island_exit.argtypes = [vp, C.c_int]
+    lib.avr_oracle_set_np_plain.argtypes = [vp, C.c_int]
+    lib.avr_oracle_simplex_closest.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.avr_oracle_narrowphase.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_double, vp]
     lib.avr_oracle_robot_fk.argtypes = [vp, C.c_int, vp]
     lib.avr_oracle_robot_self_contact.argtypes = [vp, C.c_int, vp, vp]
@@ -61,6 +63,16 @@ def lib(precision='f64', task=0):
     if key not in _LIBS:
         _LIBS[key] = _load(precision, task)
     return _LIBS[key]
+
+
+def simplex_closest(W, dbl=False, precision='f64', task=0):
+    """Test-only: the GJK's closest-point solve on the simplex with vertex rows W (1..4, 3)
+    (simplex_closest, or simplex_closest_dbl -- the stall rerun's -- with dbl).  Returns (rc,
+    vertices kept, closest point (3,), weights (4,)); rc 1: origin inside / no usable face."""
+    W = np.ascontiguousarray(W, np.float64).reshape(-1, 3)
+    out = np.zeros(8)
+    rc = lib(precision, task).avr_oracle_simplex_closest(W.ctypes.data, len(W), int(bool(dbl)), out.ctypes.data)
+    return rc, int(out[0]), out[1:4].copy(), out[4:8].copy()
 
 
 class Oracle:
@@ -123,6 +135,10 @@ class Oracle:
     def set_island_exit(self, on=True):
         """Test-only: the PGS residual exit per island instead of per env (solve_islands)."""
         self.lib.avr_oracle_set_island_exit(self.h, int(bool(on)))
+
+    def set_np_plain(self, on=True):
+        """Test-only: the narrowphase without the lane GJK's stall rule (what the rule repairs)."""
+        self.lib.avr_oracle_set_np_plain(self.h, int(bool(on)))
 
     def stats(self):
         s = np.zeros(6, np.int64)      # GJK runs, EPA runs, rows built, PGS iterations, PGS solves, stall reruns

@@ -171,6 +171,24 @@ def test_hull_sphere_gjk_epa_vs_bruteforce(scene, orc, offset):
     assert checked >= 3
 
 
+@pytest.mark.parametrize('precision,scale', [('f64', 1e160), ('f32', 1e25)])
+@pytest.mark.parametrize('dbl', [False, True], ids=['simplex_closest', 'simplex_closest_dbl'])
+def test_simplex_with_no_usable_face_is_penetrating(oracle_built, precision, scale, dbl):
+    """The GJK's closest-point solve on a tetrahedron whose only face towards the origin has a
+    non-finite distance: (2, 0, 0), (3, 0, 0), (2, 1, 0), (2, 0, 1), scaled.  At scale 1 the answer
+    is the vertex (2, 0, 0) alone.  Scaled so that the squared distance 4 scale^2 overflows the
+    build's real (every other face has the origin in its plane or behind it), no face can be
+    chosen: the solve answers "penetrating" with zero weights, as the kernel's simplex_closest_d
+    does on an empty ballot -- not with the first outside face, nor from an unset simplex."""
+    from oracle import oracle as O
+    W = np.array([[2, 0, 0], [3, 0, 0], [2, 1, 0], [2, 0, 1.0]])
+    rc, n, v, lam = O.simplex_closest(W, dbl, precision)
+    assert (rc, n) == (0, 1) and np.array_equal(v, [2, 0, 0]) and lam[0] == 1
+    rc, n, v, lam = O.simplex_closest(W * scale, dbl, precision)
+    assert rc == 1
+    assert np.array_equal(v, np.zeros(3)) and np.array_equal(lam, np.zeros(4))
+
+
 # ----------------------------------------------------------------------------- kinematics
 def test_fk_matches_independent_numpy_fk(scene, orc):
     A, md = scene
