@@ -482,6 +482,11 @@ int avr_create(const avr_config *cfg, const avr_model_desc *d, avr_sim **out) {
     k.rowstride = (RWC + ROBW) * k.rowcap;
     k.rows_envs = (int)E;
     k.b4_global = getenv("AVR_B4_GLOBAL") && getenv("AVR_B4_GLOBAL")[0] == '1';
+    // dynamics role in the pair launch: on where the role fits the pair kernel's LDS (K_DYN_ROLE: FeedingJaco);
+    // AVR_DYN_SPLIT=0|1 overrides (results are the same either way, bit for bit)
+    k.dyn_split = K_DYN_ROLE;
+    if (const char *ds = getenv("AVR_DYN_SPLIT"))
+        if (ds[0] == '0' || ds[0] == '1') k.dyn_split = K_DYN_ROLE && ds[0] == '1';
     if (E * (size_t)k.rowstride * sizeof(float) >= 0x7fff0000ull) {
         int r = fail(s, -2, "n_envs %d exceeds the row-buffer addressing limit (%d per handle)", cfg->n_envs, (int)(0x7fff0000ull / (k.rowstride * sizeof(float))));
         return r;
@@ -503,6 +508,11 @@ int avr_create(const avr_config *cfg, const avr_model_desc *d, avr_sim **out) {
         HIPCHK(s, hipMemset(cscr, 0, E * (size_t)CS_WORDS * sizeof(float)));
         s->allocs.push_back(cscr);
         k.cscr = cscr;
+        float *dynho = nullptr;
+        HIPCHK(s, hipMalloc(&dynho, E * (size_t)HO_WORDS * sizeof(float)));
+        HIPCHK(s, hipMemset(dynho, 0, E * (size_t)HO_WORDS * sizeof(float)));
+        s->allocs.push_back(dynho);
+        k.dynho = dynho;
     }
     {
         long long *st = nullptr;      // per env group: the step index (take_step) and, in a rollout, the step's slot
@@ -663,6 +673,7 @@ void *avr_stream(avr_sim *s) { return s ? (void *)s->stream : nullptr; }
 void *avr_state_device_ptr(avr_sim *s) { return s ? (void *)s->d_state : nullptr; }
 int32_t avr_n_envs(avr_sim *s) { return s ? s->cfg.n_envs : 0; }
 int32_t avr_env_groups(avr_sim *s) { return s ? s->ngroups : 0; }
+int32_t avr_dyn_split(const avr_sim *s) { return s ? s->km.dyn_split : 0; }
 
 #define CHECK_SIM(s)                         \
     if (!(s) || !(s)->d_state) return -1;    \

@@ -122,8 +122,42 @@ struct PairsLDS {
         } u;
     };
 };
+// LDS of the pair launch's dynamics role (dyn_env): the members of EnvLDS that the unconstrained
+// velocities and the non-contact rows use, under the same names, so that the device functions
+// templated on the LDS type serve both.  It shares the pair kernel's LDS block with PairsLDS (a
+// block runs one role), within the same 10 KB.
+#if K_DYN_ROLE
+struct DynLDS {
+    float st[S_CP];
+    float cm[MAXL][8], ax[MAXL][4], org[MAXL][4];
+    float vq[MAXD];
+    float fv[MAXF][4], fw[MAXF][4];
+    float Iinv[MAXF][12];
+    float gsc[MAXF][4];
+    float h[MAXD], qdd[MAXD];
+    int n_nc, flags, gender, nla, nda;
+#ifdef AVR_PROF
+    unsigned long long prof[AVR_PROF_SLOTS];
+#endif
+    union __attribute__((aligned(16))) {   // EnvLDS's phase overlay without the contact update
+        float lk[MAXL][8];
+        struct {
+            union {
+                float rn[6][MAXL][4];
+                float Mi[MAXD][MAXD];
+            };
+            float iw[MAXL][8];
+            float Minv[MAXD][MAXD];
+        } d;
+    } u;
+};
+union PairsBlockLDS { PairsLDS p; DynLDS d; };
+static_assert(sizeof(((DynLDS *)0)->u.d.rn) - sizeof(((DynLDS *)0)->u.d.rn[0]) >= 12 * MAXD * sizeof(float), "weld row scratch");
+#else
+union PairsBlockLDS { PairsLDS p; };
+#endif
 #ifndef AVR_PROF
-static_assert(sizeof(PairsLDS) <= 10240, "pair kernel: 16 blocks per CU");
+static_assert(sizeof(PairsBlockLDS) <= 10240, "pair kernel: 16 blocks per CU");
 static_assert(MAXSH % 64 == 0, "shape info staged 64 per pass");
 #endif
 
@@ -160,6 +194,9 @@ AVR_DI int lgo(const LT &L, const KModel &m) { return L.gender * m.nla; }   // g
 // robot_fk's joint-frame scratch: a member of EnvLDS's phase union, of PairsLDS's FK struct
 AVR_DI float (*lk_of(EnvLDS &L))[8] { return L.u.lk; }
 AVR_DI float (*lk_of(PairsLDS &L))[8] { return L.lk; }
+#if K_DYN_ROLE
+AVR_DI float (*lk_of(DynLDS &L))[8] { return L.u.lk; }
+#endif
 
 template <class LT>
 AVR_DI void robot_fk(const KModel &m, LT &L) {
@@ -249,8 +286,8 @@ AVR_DI void dof_col(const KModel &m, const EnvLDS &L, int j, v3 p, v3 &lin, v3 &
 // x = M^-1 e_c for a column c of the block [B0, B1) of the block-diagonal factor (entries of x
 // outside the block are 0): forward / back substitution over the block only -- the full-size solve
 // on e_c adds nothing but products with exact zeros (the other block, the zero head of y)
-template <int B0, int B1>
-AVR_DI void chol_solve_block(const EnvLDS &L, int c, float *x) {
+template <int B0, int B1, class LT>
+AVR_DI void chol_solve_block(const LT &L, int c, float *x) {
     float y[MAXD];
 #pragma unroll
     for (int i = 0; i < MAXD; i++) { y[i] = 0.f; x[i] = 0.f; }
@@ -270,7 +307,8 @@ AVR_DI void chol_solve_block(const EnvLDS &L, int c, float *x) {
     }
 }
 
-AVR_DI bool robot_mass_matrix(const KModel &m, EnvLDS &L) {
+template <class LT>
+AVR_DI bool robot_mass_matrix(const KModel &m, LT &L) {
     PROF_START(pm);
     const int nd = L.nda;
     const int go = lgo(L, m);
@@ -396,8 +434,8 @@ AVR_DI void minv_mul(const EnvLDS &L, const float *x, float *y) {
 // sums, leaving them unchanged: the same bits with K_ND^2 (robot) instead of MAXD^2 products -- the
 // serial tail of an env's contact rows when one lane holds a robot contact (FeedingJaco: 100 of 196
 // products per row; the PR2 tasks 196 of 576)
-template <int LO, int HI>
-AVR_DI void minv_mul_blk(const EnvLDS &L, const float *x, float *y) {
+template <int LO, int HI, class LT>
+AVR_DI void minv_mul_blk(const LT &L, const float *x, float *y) {
 #if AVR_MINV_LAUNDER
     int z = 0;
     asm volatile("" : "+v"(z));
@@ -451,8 +489,8 @@ AVR_DI void minv_mul_add(const KModel &m, const EnvLDS &L, int link, const float
 }
 
 // entry d of M^-1 x within the block [LO, HI) of M (minv_mul_blk's sum for row d; one lane per row)
-template <int LO, int HI>
-AVR_DI float minv_entry(const EnvLDS &L, const float *x, int d) {
+template <int LO, int HI, class LT>
+AVR_DI float minv_entry(const LT &L, const float *x, int d) {
     if (d < LO || d >= HI) return 0.f;
     const float *Mv = &L.u.d.Minv[0][0] + d * MAXD;
     float s = 0.f;
@@ -496,7 +534,8 @@ AVR_DI v3 anc_sum3(const KModel &m, unsigned am, const float (*A)[4], const floa
     return acc;
 }
 
-AVR_DI void robot_bias(const KModel &m, EnvLDS &L) {
+template <class LT>
+AVR_DI void robot_bias(const KModel &m, LT &L) {
     float (*R0)[4] = L.u.d.rn[0], (*R1)[4] = L.u.d.rn[1], (*R2)[4] = L.u.d.rn[2], (*R3)[4] = L.u.d.rn[3], (*R4)[4] = L.u.d.rn[4], (*R5)[4] = L.u.d.rn[5];
     const float k1l = m.lin_damp, k1a = m.ang_damp;
     const int i = lane_id();
@@ -2123,7 +2162,8 @@ AVR_DI void collide_contacts(const KModel &m, EnvLDS &L, const float *cs, float 
 // and the wave-cooperative row (one DoF per lane) round alike: left to contraction, the compiler
 // fuses different products of the two forms (which product of a sum it fuses depends on how
 // often each is used after CSE).
-AVR_DI float jac_entry(const KModel &m, const EnvLDS &L, unsigned am, int d, v3 p, v3 lin, v3 ang) {
+template <class LT>
+AVR_DI float jac_entry(const KModel &m, const LT &L, unsigned am, int d, v3 p, v3 lin, v3 ang) {
     float v = 0.f;
     if (d < m.nd + m.hc_n) {               // chain DoFs are never ancestors of a robot link
         const int k = gld(m.dof_link + (d));
@@ -2140,17 +2180,20 @@ AVR_DI float jac_entry(const KModel &m, const EnvLDS &L, unsigned am, int d, v3 
     }
     return v;
 }
-AVR_DI void robot_jac(const KModel &m, const EnvLDS &L, int link, v3 p, v3 lin, v3 ang, float *J) {
+template <class LT>
+AVR_DI void robot_jac(const KModel &m, const LT &L, int link, v3 p, v3 lin, v3 ang, float *J) {
     const unsigned am = gld(m.anc_mask + (link));
 #pragma unroll
     for (int d = 0; d < MAXD; d++) J[d] = jac_entry(m, L, am, d, p, lin, ang);
 }
 
-AVR_DI float free_dot(const EnvLDS &L, int f, v3 lin, v3 ang) {
+template <class LT>
+AVR_DI float free_dot(const LT &L, int f, v3 lin, v3 ang) {
     return dot(lin, ld3(L.fv[f])) + dot(ang, ld3(L.fw[f]));
 }
 
-AVR_DI v3 iinv_mul(const EnvLDS &L, int f, v3 a) {
+template <class LT>
+AVR_DI v3 iinv_mul(const LT &L, int f, v3 a) {
     const float *I = L.Iinv[f];
     return V(I[0] * a.x + I[1] * a.y + I[2] * a.z, I[3] * a.x + I[4] * a.y + I[5] * a.z, I[6] * a.x + I[7] * a.y + I[8] * a.z);
 }
@@ -2229,7 +2272,8 @@ AVR_DI float *row_rob(const KModel &m, float *base, int slot) { return base + m.
 #error "B4_FPAIR: the second friction row's 4th header word now holds its residual limit, not the coupling"
 #endif
 static_assert(!K_TORSION || MAXF == 1, "the torsional index shares the normal header's word 0 with a 1-body ownership mask");
-AVR_DI void put_free(const EnvLDS &L, int f, float *w, v3 jl, v3 ja) {
+template <class LT>
+AVR_DI void put_free(const LT &L, int f, float *w, v3 jl, v3 ja) {
     const float *g = L.gsc[f];
     const qt q = ldq(L.st + S_FREE + AVR_FB_WORDS * f + 3);
     const v3 b = qrot(qconj(q), ja);
@@ -2272,7 +2316,8 @@ __device__ int g_coop_check;     // (diagnostic build: mismatches reported)
 // Non-contact rows (limits, motors, fixed constraint), one lane per row.
 // Row order restates btMultiBodyConstraintSolver's setup order: joint-limit rows
 // of violated limits (link order, lower then upper), motor rows (link order), fixed rows.
-AVR_DI int build_noncontact_rows(const KModel &m, EnvLDS &L, float *rows, float dt) {
+template <class LT>
+AVR_DI int build_noncontact_rows(const KModel &m, LT &L, float *rows, float dt) {
     const int lane = lane_id();
     const float erp = m.erp;
     // enumerate in parallel (lane l = link l: its violated limits, then its motor), number the rows
@@ -2754,25 +2799,23 @@ AVR_DI int build_contact_rows(const KModel &m, EnvLDS &L, const float *gcp, floa
 
 // --------------------------------------------------------------------------- one sub-step
 // A sub-step is four kernels: avr_substep_pairs_kernel (forward kinematics, body frames,
-// broadphase, shape-pair list), avr_narrowphase_kernel (one lane per listed shape pair, across
-// all envs), avr_substep_a_kernel (the rare pairs that need the wave-cooperative narrowphase,
-// then manifold update, unconstrained velocities, constraint rows) and avr_substep_b4_kernel
-// (PGS + integration).  What crosses the kernel boundaries goes
-// through the per-env collision scratch (m.cscr), the workspace (m.ws) and the row buffer
-// (m.rows).
-AVR_DI bool substep_a(const KModel &m, EnvLDS &L, float dt, float *gst, float *ws, float *rows, const float *cs) {
+// broadphase, shape-pair list; with the dynamics split on, a second block per env runs the
+// unconstrained velocities and the non-contact rows beside it: dyn_env), avr_narrowphase_kernel
+// (one lane per listed shape pair, across all envs), avr_substep_a_kernel (the rare pairs that
+// need the wave-cooperative narrowphase, then manifold update and contact rows; with the split
+// off also the unconstrained velocities and non-contact rows, between the two) and
+// avr_substep_b4_kernel (PGS + integration).  What crosses the kernel boundaries goes
+// through the per-env collision scratch (m.cscr), the workspace (m.ws), the row buffer
+// (m.rows) and the dynamics hand-over (m.dynho).
+
+// Unconstrained velocities of a sub-step: M^-1 and the bias forces of the articulated system, its
+// velocities after dt (vq), the free bodies' (fv, fw) with their world inverse inertias and
+// mass-normalisation scales.  Reads the state words and the link frames only.  Returns whether the
+// mass matrix factored.
+template <class LT>
+AVR_DI bool unconstrained_velocities(const KModel &m, LT &L, float dt) {
     const int lane = lane_id();
     PROF_START(ps);
-    // (the body and link frames from the pair kernel and the previous contact pool were staged
-    // by load_a)
-    PROF_STOP(0, ps);
-    collide_contacts(m, L, cs, gst + S_CP);
-    PROF_STOP(13, ps);
-#ifdef AVR_LDS_POISON   // (the dynamics overlay the contact update's storage: re-poison it)
-    for (int i = lane; i < (int)(sizeof(L.u) / 4); i += 64) ((float *)&L.u)[i] = __int_as_float(-1);
-    SYNC();
-#endif
-    // unconstrained velocities
     bool ok = robot_mass_matrix(m, L);
     PROF_START(pbias);
     robot_bias(m, L);
@@ -2816,20 +2859,61 @@ AVR_DI bool substep_a(const KModel &m, EnvLDS &L, float dt, float *gst, float *w
     }
     SYNC();
     PROF_STOP(6, ps);
-    const int n_nc = build_noncontact_rows(m, L, rows, dt);
-    PROF_STOP(7, ps);
-    const int n_rob = build_contact_rows(m, L, gst + S_CP, rows, n_nc, dt);
-    SYNC();
-    PROF_STOP(8, ps);
-    // hand-over to part B
-    if (lane == 0) {
-        ws[WS_NNC] = __int_as_float(n_nc); ws[WS_NC] = __int_as_float(L.n_c); ws[WS_NROB] = __int_as_float(n_rob);
-        ws[WS_NT] = __int_as_float(K_TORSION ? L.n_t : 0);
-    }
+    return ok;
+}
+
+// The unconstrained velocities' hand-over to part B (workspace words)
+template <class LT>
+AVR_DI void store_velocities(const KModel &m, const LT &L, float *ws) {
+    const int lane = lane_id();
     if (lane < MAXD) ws[WS_VQ + lane] = lane < L.nda ? L.vq[lane] : 0.f;
     if (lane < m.nf) {
         st3(ws + WS_FV + 4 * lane, ld3(L.fv[lane]));
         st3(ws + WS_FW + 4 * lane, ld3(L.fw[lane]));
+    }
+}
+
+AVR_DI int load_handover(const KModel &m, EnvLDS &L, const float *ho, const float *ws, bool &ok, int &flags);   // (beside load_a)
+
+AVR_DI bool substep_a(const KModel &m, EnvLDS &L, float dt, float *gst, float *ws, float *rows, const float *cs, const float *ho) {
+    const int lane = lane_id();
+    PROF_START(ps);
+    // (the body and link frames from the pair kernel and the previous contact pool were staged
+    // by load_a)
+    PROF_STOP(0, ps);
+    collide_contacts(m, L, cs, gst + S_CP);
+    PROF_STOP(13, ps);
+#ifdef AVR_LDS_POISON   // (the dynamics overlay the contact update's storage: re-poison it)
+    for (int i = lane; i < (int)(sizeof(L.u) / 4); i += 64) ((float *)&L.u)[i] = __int_as_float(-1);
+    SYNC();
+#endif
+    bool ok;
+    int n_nc;
+    const bool split = K_DYN_ROLE && m.dyn_split;
+    if (split) {
+        // the dynamics role ran them in the pair launch
+        int hf;
+        n_nc = load_handover(m, L, ho, ws, ok, hf);
+        if (lane == 0) L.flags |= hf;
+        PROF_STOP(6, ps);
+    } else {
+        ok = unconstrained_velocities(m, L, dt);
+        PROF_START(pn);
+        n_nc = build_noncontact_rows(m, L, rows, dt);
+        PROF_STOP(7, pn);
+    }
+    PROF_START(pc);
+    const int n_rob = build_contact_rows(m, L, gst + S_CP, rows, n_nc, dt);
+    SYNC();
+    PROF_STOP(8, pc);
+    // hand-over to part B
+    if (lane == 0) {
+        ws[WS_NC] = __int_as_float(L.n_c); ws[WS_NROB] = __int_as_float(n_rob);
+        ws[WS_NT] = __int_as_float(K_TORSION ? L.n_t : 0);
+    }
+    if (!split) {
+        if (lane == 0) ws[WS_NNC] = __int_as_float(n_nc);
+        store_velocities(m, L, ws);
     }
     return ok;
 }
@@ -2921,6 +3005,7 @@ AVR_DI int xcc_id() {   // XCD of the executing CU (HW_REG_XCC_ID, id 20, bits 3
 
 AVR_DI float *env_ws(const KModel &m, int env) { return m.ws + (size_t)env * WS_WORDS; }
 AVR_DI float *env_rows(const KModel &m, int env) { return m.rows + (size_t)env * (size_t)m.rowstride; }
+AVR_DI float *env_dynho(const KModel &m, int env) { return m.dynho + (size_t)env * HO_WORDS; }
 
 AVR_DI bool env_hdyn(const KModel &m, const float *gst) { return m.hc_n > 0 && gst[S_TASK + T_HDYN] != 0.f; }
 
@@ -3006,6 +3091,32 @@ AVR_DI void load_a(const KModel &m, EnvLDS &L, const float *gst, const float *cs
     if (lane < AVR_PROF_SLOTS) L.prof[lane] = 0;
 #endif
     SYNC();
+}
+
+// Kernel a with the dynamics split on: what the pair launch's dynamics role (dyn_env) left for
+// the contact rows -- M^-1, the unconstrained velocities, the free bodies' inverse inertias and
+// scales -- into the EnvLDS fields the split-off path computes in place, with every load in flight
+// before the first LDS store.  Returns the non-contact row count; ok and flags as handed over.
+AVR_DI int load_handover(const KModel &m, EnvLDS &L, const float *ho, const float *ws, bool &ok, int &flags) {
+    float tm[NB_OF(MAXD * MAXD)], ti[NB_OF(MAXF * 12)], tg[NB_OF(MAXF * 4)], tq[NB_OF(MAXD)], tv[NB_OF(MAXF * 4)], tw[NB_OF(MAXF * 4)];
+    g2r(tm, ho + HO_MINV, MAXD * MAXD);
+    g2r(ti, ho + HO_IINV, m.nf * 12);
+    g2r(tg, ho + HO_GSC, m.nf * 4);
+    g2r(tq, ws + WS_VQ, MAXD);
+    g2r(tv, ws + WS_FV, m.nf * 4);
+    g2r(tw, ws + WS_FW, m.nf * 4);
+    const int n_nc = __float_as_int(gld(ho + HO_NNC));
+    ok = __float_as_int(gld(ho + HO_OK)) != 0;
+    flags = __float_as_int(gld(ho + HO_FLAGS));
+    r2l(&L.u.d.Minv[0][0], tm, MAXD * MAXD);
+    r2l(&L.Iinv[0][0], ti, m.nf * 12);
+    r2l(&L.gsc[0][0], tg, m.nf * 4);
+    r2l(L.vq, tq, MAXD);
+    r2l(&L.fv[0][0], tv, m.nf * 4);
+    r2l(&L.fw[0][0], tw, m.nf * 4);
+    if (lane_id() == 0) L.n_nc = n_nc;
+    SYNC();
+    return n_nc;
 }
 
 template <class LT>
@@ -3107,11 +3218,62 @@ AVR_DI void pairs_env(const KModel &m, PairsLDS &L, float *__restrict__ state, i
     prof_flush(m, L, env);
 }
 
+#if K_DYN_ROLE
+// The pair launch's dynamics role (m.dyn_split): one more 64-lane block per env, beside the env's
+// pairs_env block -- forward kinematics on its own LDS, then the unconstrained velocities and the
+// non-contact rows, which read only the state part B left and the link frames.  They would
+// otherwise open kernel a's row building, two launches later on the sub-step's chain.  Writes the
+// env's non-contact rows (row buffer), the workspace words part B reads (WS_VQ, WS_FV, WS_FW,
+// WS_NNC) and the hand-over for kernel a's contact rows (m.dynho); no state word (pairs_env
+// writes none either: its results go to the collision scratch).
+AVR_DI void dyn_env(const KModel &m, DynLDS &L, const float *__restrict__ state, float dt, int env) {
+    const int lane = lane_id();
+    const float *gst = state + (size_t)env * K_STATE_WORDS;
+    load_state(m, L, gst);
+    PROF_START(ps);
+    robot_fk(m, L);
+    PROF_STOP(0, ps);
+    const bool ok = unconstrained_velocities(m, L, dt);
+    PROF_START(pn);
+    const int n_nc = build_noncontact_rows(m, L, env_rows(m, env), dt);
+    SYNC();
+    PROF_STOP(7, pn);
+    float *ws = env_ws(m, env), *ho = env_dynho(m, env);
+    store_velocities(m, L, ws);
+    for (int i = lane; i < MAXD * MAXD; i += 64) ho[HO_MINV + i] = (&L.u.d.Minv[0][0])[i];
+    for (int i = lane; i < m.nf * 12; i += 64) ho[HO_IINV + i] = (&L.Iinv[0][0])[i];
+    for (int i = lane; i < m.nf * 4; i += 64) ho[HO_GSC + i] = (&L.gsc[0][0])[i];
+    if (lane == 0) {
+        ws[WS_NNC] = __int_as_float(n_nc);
+        ho[HO_NNC] = __int_as_float(n_nc); ho[HO_OK] = __int_as_float(ok ? 1 : 0); ho[HO_FLAGS] = __int_as_float(L.flags);
+    }
+    prof_flush(m, L, env);
+}
+#endif
+
+// Grid: one block per env (blockIdx.x = env - env0); with the dynamics split on, 16 blocks per 8
+// envs in the narrowphase kernel's mapping -- blocks 16 k .. 16 k + 7 the pair role of envs
+// 8 k .. 8 k + 7, blocks 16 k + 8 .. 16 k + 15 their dynamics role -- so that both blocks of an env
+// run on the XCD (block index mod 8) of the env's other kernels and both roles start early.
 __global__ __launch_bounds__(64) AVR_KATTR void avr_substep_pairs_kernel(const KModel *__restrict__ mp, float *__restrict__ state,
-                                                                         const unsigned char *__restrict__ mask, int env0, int n_envs) {
-    __shared__ PairsLDS L;
+                                                                         const unsigned char *__restrict__ mask, float dt, int env0, int n_envs) {
+    __shared__ PairsBlockLDS L;
+#if K_DYN_ROLE
+    if (mp->dyn_split) {
+        const int b = blockIdx.x;
+        const int env = env0 + 8 * (b >> 4) + (b & 7);
+        if (env >= n_envs) return;
+        if (mask && !mask[env]) return;
+        const KModel &m = *mp;
+        if ((b >> 3) & 1) dyn_env(m, L.d, state, dt, env);
+        else pairs_env(m, L.p, state, env);
+        return;
+    }
+#else
+    (void)dt;
+#endif
     AVR_ENV_GUARD();
-    pairs_env(m, L, state, env);
+    pairs_env(m, L.p, state, env);
 }
 
 // Sphere against convex hull (most of the scene's shape pairs: food against the spoon's and the
@@ -3495,7 +3657,8 @@ __global__ __launch_bounds__(64) void avr_coop_kernel(const KModel *__restrict__
 
 // Sub-step part A3: one 64-lane block per env, state staged in LDS -- the pairs the narrowphase
 // kernel left to the wave-cooperative path (rc 2: EPA, big hulls; 0.2-0.3 per env-step), then
-// manifold update, unconstrained velocities, constraint rows.  The cooperative pairs open this
+// manifold update and contact rows; between the two, the unconstrained velocities and the
+// non-contact rows, or (dynamics split) the load of what the pair launch's dynamics role left.  The cooperative pairs open this
 // kernel rather than a kernel of their own: the few envs that have one (an EPA can take ~40 us)
 // delay only their own wave, not a whole launch that every env's kernel a waits behind.
 AVR_DI void substep_a_env(const KModel &m, EnvLDS &L, float *__restrict__ state, float dt, int env, int n_envs) {
@@ -3530,7 +3693,7 @@ AVR_DI void substep_a_env(const KModel &m, EnvLDS &L, float *__restrict__ state,
     }
     SYNC();
 #endif
-    bool ok = substep_a(m, L, dt, gst, env_ws(m, env), env_rows(m, env), env_cs(m, env));
+    bool ok = substep_a(m, L, dt, gst, env_ws(m, env), env_rows(m, env), env_cs(m, env), K_DYN_ROLE ? env_dynho(m, env) : nullptr);
 #ifdef AVR_PROF
     if (lane_id() == 0) env_ws(m, env)[WS_XCC] = __int_as_float(xcc_id());
 #endif
@@ -4469,7 +4632,9 @@ hipError_t avr_launch_step(const KModel *h_m, const KModel *d_m, float *state, c
     // enforce_hard_human_joint_limits (env.py:342-343); the reset's settle frames do not
     auto sub = [&](float h, int frame_end) {
         mark(AVR_K_PAIRS);
-        hipLaunchKernelGGL(avr_substep_pairs_kernel, dim3(n_envs), dim3(64), 0, stream, d_m, state, mask, env0, env1);
+        // (dynamics split: the pair role's and the dynamics role's blocks, in alternating runs of 8)
+        hipLaunchKernelGGL(avr_substep_pairs_kernel, dim3(K_DYN_ROLE && h_m->dyn_split ? 16 * ((n_envs + 7) / 8) : n_envs), dim3(64), 0, stream, d_m, state,
+                           mask, h, env0, env1);
         mark(AVR_K_NARROW);
         hipLaunchKernelGGL(avr_narrowphase_kernel, dim3(16 * ((n_envs + 8 * NP_ENVS - 1) / (8 * NP_ENVS))), dim3(64), 0, stream, d_m, mask, env0, env1);
 #if AVR_COOP_KERNEL

@@ -37,9 +37,11 @@ static_assert(MAXD <= 16 * NDL && MAXL <= 32, "DoF slots per lane / 32-bit link 
 
 
 // Per-env collision scratch (m.cscr, CS_WORDS floats per env), the hand-over between the three
-// kernels of a sub-step's part A: avr_substep_pairs_kernel writes the shape-pair list, the body
-// COM frames and the link frames; avr_narrowphase_kernel writes one result per pair;
-// avr_substep_a_kernel consumes them.
+// kernels of a sub-step's part A: avr_substep_pairs_kernel's pair role writes the shape-pair list,
+// the body COM frames and the link frames; avr_narrowphase_kernel writes one result per pair;
+// avr_substep_a_kernel consumes them (manifold update, contact rows).  With the dynamics split on
+// (m.dyn_split) the pair launch's dynamics role hands kernel a the rest of what its contact rows
+// need through m.dynho (HO_*, below).
 #define CS_NSP 0                                    // int bits: shape pairs
 #define CS_FLAGS 1                                  // int bits: flags raised by the pair kernel
 #define CS_N0 2                                     // int bits: sphere-hull pairs (list CS_L0)
@@ -54,6 +56,17 @@ static_assert(MAXD <= 16 * NDL && MAXL <= 32, "DoF slots per lane / 32-bit link 
 #define CS_L1 (CS_L0 + 2 * MAXSP)                   // [MAXSP][2] the other pairs, ascending, the same entries
 #define CS_COOP (CS_L1 + 2 * MAXSP)                 // nonzero: some pair of this sub-step was left to the coop kernel (rc 2)
 #define CS_WORDS (CS_COOP + 4)                      // (keeps every env's CS_RES 16-byte aligned)
+// Per-env dynamics hand-over (m.dynho, HO_WORDS floats per env), written by the pair launch's
+// dynamics role and read by kernel a's contact rows when m.dyn_split is set.  The unconstrained
+// velocities and the non-contact row count go through the workspace (WS_VQ, WS_FV, WS_FW, WS_NNC),
+// where part B reads them.
+#define HO_MINV 0                                   // [MAXD][MAXD] M^-1
+#define HO_IINV (HO_MINV + MAXD * MAXD)             // [MAXF][12] world inverse inertias
+#define HO_GSC (HO_IINV + 12 * MAXF)                // [MAXF][4] mass-normalisation scales
+#define HO_NNC (HO_GSC + 4 * MAXF)                  // int bits: non-contact rows
+#define HO_OK (HO_NNC + 1)                          // int bits: the mass matrix factored (0: kernel a raises flag bit 0)
+#define HO_FLAGS (HO_NNC + 2)                       // int bits: flag bits the row builder raised
+#define HO_WORDS ((HO_NNC + 3 + 3) & ~3)
 static_assert(MAXB <= 256 && MAXSP <= 65536, "narrowphase list entries pack k (16 bits) and two body indices (8 bits each)");
 
 // Articulated links: the robot's nl links, then (impairment 'tremor') the head/neck chain's
@@ -120,6 +133,9 @@ struct KModel {
     int rowstride;             // floats between consecutive envs' row buffers
     int rows_envs;             // envs covered by the row buffer (the handle's n_envs)
     int b4_global;             // diagnostic (AVR_B4_GLOBAL=1): part B reads every row from global memory
+    int dyn_split;             // the pair launch runs the dynamics role (AVR_DYN_SPLIT; per-task default): unconstrained
+                               // velocities and non-contact rows there, kernel a keeps the manifold update and contact rows
+    float *dynho;              // per-env dynamics hand-over between the dynamics role and kernel a: [n_envs][HO_WORDS]
     float *ws;                 // per-env workspace between sub-step kernels: [n_envs][128]
     float *cscr;               // per-env collision scratch between the part-A kernels: [n_envs][CS_WORDS]
     unsigned long long *prof;  // diagnostic builds only (AVR_PROF): [n_envs][16] cycle counters

@@ -161,6 +161,11 @@ int32_t avr_n_envs(avr_sim *sim);
  * (one per 1024 envs, at most 4; AVR_ENV_GROUPS=1..8 in the environment at avr_create overrides).
  * Results do not depend on it.  No reference counterpart (diagnostic). */
 int32_t avr_env_groups(avr_sim *sim);
+/* 1 when the handle's sub-steps run the dynamics role in the pair launch (unconstrained velocities
+ * and non-contact rows beside the pair enumeration instead of inside kernel a; FeedingJaco's
+ * default, AVR_DYN_SPLIT=0|1 in the environment at avr_create overrides), else 0.  Results do not
+ * depend on it.  No reference counterpart (diagnostic). */
+int32_t avr_dyn_split(const avr_sim *sim);
 /* Graph captures made by this handle so far (each distinct step key captures once; a few keys
  * are cached).  No reference counterpart (diagnostic). */
 int64_t avr_graph_captures(avr_sim *sim);
