@@ -22,6 +22,7 @@ EXPORTS = [
     'avr_get_q', 'avr_get_link_pose', 'avr_get_contact_summary', 'avr_get_flags', 'avr_reset_ik', 'avr_base_search',
     'avr_graph_captures', 'avr_robot_self_contact', 'avr_narrowphase_query', 'avr_bb_closest_query',
     'avr_policy_set', 'avr_policy_act_device', 'avr_rollout_policy_device',
+    'avr_reset_pool_set', 'avr_rollover_enable', 'avr_rollover_device', 'avr_rollover_buffers', 'avr_rollover_set_episodes',
 ]
 FLAGS_FAULT_MASK = 0x1f      # include/avr.h AVR_FLAGS_FAULT_MASK: bits 0-4; bit 5 (EPA budget) is informational
 
@@ -76,6 +77,12 @@ def load(path=LIB_PATH):
         lib.avr_policy_set.argtypes = [vp, C.POINTER(avr_policy_desc)]
         lib.avr_policy_act_device.argtypes = [vp, C.c_int64, vp, C.c_int32, vp, vp, vp]
         lib.avr_rollout_policy_device.argtypes = [vp, C.c_int64, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, 'avr_reset_pool_set'):          # (absent in experiment builds of older trees)
+        lib.avr_reset_pool_set.argtypes = [vp, C.c_int32, vp, vp]
+        lib.avr_rollover_enable.argtypes = [vp, C.c_int32]
+        lib.avr_rollover_device.argtypes = [vp, vp, vp]
+        lib.avr_rollover_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        lib.avr_rollover_set_episodes.argtypes = [vp, vp]
     lib.avr_sync.argtypes = [vp]
     lib.avr_stream.argtypes = [vp]
     lib.avr_stream.restype = vp
@@ -322,6 +329,35 @@ class Sim:
         self._chk(self.lib.avr_rollout_policy_device(self.h, int(t0), int(n), d_obs0, int(bool(deterministic)), d_obs, d_act, d_logp, d_value,
                                                      d_rew, d_done, d_info))
 
+    # ---- device-side episode rollover from a reset-state pool (include/avr.h avr_rollover_*)
+    def reset_pool_set(self, S, obs):
+        """Install (or, with at most as many rows as the first pool, replace) the reset-state pool:
+        S (n_pool, state words) settled reset states as get_state returns them, obs (n_pool, obs_dim)
+        their reset observations.  No graph is re-captured."""
+        S = np.ascontiguousarray(S, np.float32)
+        obs = np.ascontiguousarray(obs, np.float32)
+        assert S.ndim == 2 and S.shape[1] == self.words and obs.shape == (len(S), self.obs_dim)
+        self._chk(self.lib.avr_reset_pool_set(self.h, int(len(S)), S.ctypes.data, obs.ctypes.data))
+
+    def rollover_enable(self, on=True):
+        """The rollover mode of the rollouts: envs a step finishes take their next state from the pool."""
+        self._chk(self.lib.avr_rollover_enable(self.h, int(bool(on))))
+
+    def rollover_device(self, d_done, d_obs):
+        """Roll over the envs with d_done[e] != 0 and rewrite their d_obs rows (device pointers; asynchronous)."""
+        self._chk(self.lib.avr_rollover_device(self.h, d_done, d_obs))
+
+    def rollover_buffers(self):
+        """Device pointers (term_obs [n_envs, obs_dim] float32, term_value [n_envs] float32, episode
+        [n_envs] int32) of the handle's rollover rows."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.avr_rollover_buffers(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def rollover_set_episodes(self, episodes):
+        ep = np.ascontiguousarray(episodes, np.int32).reshape(self.n)
+        self._chk(self.lib.avr_rollover_set_episodes(self.h, ep.ctypes.data))
+
     def sync(self):
         self._chk(self.lib.avr_sync(self.h))
 
@@ -447,6 +483,21 @@ def policy_noise(seed, env_ids, t, act_dim=ABI.ACT_DIM):
                 if j < act_dim:
                     out[:, j] = z
     return out
+
+
+def rollover_index(seed, env_ids, episodes, n_pool):
+    """Pool row an env's rollover takes, int64 (len(env_ids),): the host mirror of the device rollover's
+    pick (csrc/avr_rollover.hip rollover_env).  Word 0 of Philox4x32-10 keyed by seed on the counter
+    {env, episode lo, 0x40000000, episode hi}, modulo n_pool; env_ids are global ids (env_offset + e),
+    episodes the counters before the increment (a scalar or one per env).  random_actions' counter
+    word 2 is 0 or 1 and policy_noise's has the top bit set, so the three streams share no counter."""
+    if int(n_pool) < 1:
+        raise ValueError('rollover_index: n_pool must be >= 1')
+    env_ids = np.asarray(env_ids, np.uint64)
+    ep = np.broadcast_to(np.asarray(episodes, np.int64), env_ids.shape).astype(np.uint64)
+    c = [env_ids, ep & np.uint64(0xFFFFFFFF), np.full_like(env_ids, 0x40000000), ep >> np.uint64(32)]
+    r = philox4x32_10(c, seed, seed >> 32)
+    return (r[0] % np.uint64(n_pool)).astype(np.int64)
 
 
 def hull_support_table(verts, G=16):

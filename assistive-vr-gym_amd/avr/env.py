@@ -433,10 +433,25 @@ class AVRTorchVecEnv(AVRVecEnv):
     info as cuda tensors, written by the kernels directly (avr_step_device).  No per-step host
     traffic or synchronisation: whether a rollover is due follows from the host mirror of the
     iteration counters (done == T_ITER >= max_steps in the kernels), so launches of consecutive
-    steps queue ahead of the GPU; a rollover step synchronises for the reset."""
+    steps queue ahead of the GPU; a rollover step synchronises for the reset.
 
-    def __init__(self, *args, **kw):
+    reset_pool: None (default) keeps that behaviour.  reset_pool=m >= 1 moves the episode boundary onto
+    the device (include/avr.h avr_rollover_*): the first reset() runs the reset path for episodes
+    0 .. m-1 of every env (the same draws, IK and settle), collects the m * n_envs settled states and
+    reset observations into a device-resident pool, leaves the envs in the last of them and switches
+    the handle's rollover mode on.  From then on a finished env takes a pool state on the device: step()
+    neither synchronises nor resets on the host, and rollout_policy runs any n steps across episode
+    boundaries in one call.  Episodes then re-use the pool's initial states instead of drawing new ones
+    (DESIGN.md).  pool_build_s holds the time the pool took to build."""
+
+    def __init__(self, *args, reset_pool=None, **kw):
+        if reset_pool is not None and (int(reset_pool) != reset_pool or int(reset_pool) < 1):
+            raise ValueError('reset_pool must be None or an integer >= 1, not %r' % (reset_pool,))
+        self.reset_pool = None if reset_pool is None else int(reset_pool)
         super().__init__(*args, **kw)
+        if self.reset_pool and self.task == ABI.TASK_DRESSING:
+            self.sim.close()
+            raise NotImplementedError('reset_pool: the device rollover is not built for DressingJaco-v0')
         import torch
         self.torch = torch
         self.dev = torch.device('cuda', int(self.device))
@@ -449,8 +464,50 @@ class AVRTorchVecEnv(AVRVecEnv):
         self._cur = None                   # the current observation (what reset / step / rollout_policy last returned)
         self._roll = {}                    # rollout_policy's stacked output buffers, by rollout length
         self.policy_t = 0                  # rollout_policy's step index (keys the sampling noise; never reused)
+        self._pool = None                  # reset_pool: (term_obs, term_value, episode) tensors over the handle's rollover rows
+        self.pool_build_s = None
+
+    def _wrap(self, ptr, shape, typestr):
+        """A torch tensor over device memory the handle owns (no copy; valid until close())."""
+        holder = type('_DevArray', (), {})()
+        holder.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2, strides=None)
+        return self.torch.as_tensor(holder, device=self.dev)
+
+    def _build_pool(self):
+        """The reset path for episodes 0 .. m-1 of every env into the handle's reset-state pool; the
+        envs stay in the last of those resets.  The rollover rows are wrapped once."""
+        t0 = time.perf_counter()
+        every = np.ones(self.n, bool)
+        S, O = [], []
+        for ep in range(self.reset_pool):
+            self.episode[:] = ep
+            self._reset_rows(every)
+            S.append(self.sim.get_state())
+            O.append(self._obs.copy())
+        self.sim.reset_pool_set(np.concatenate(S), np.concatenate(O))
+        self.sim.rollover_enable(True)
+        self.sim.rollover_set_episodes(self.episode)
+        to, tv, ep = self.sim.rollover_buffers()
+        self._pool = (self._wrap(to, (self.n, self.L.OBS_DIM), '<f4'), self._wrap(tv, (self.n,), '<f4'), self._wrap(ep, (self.n,), '<i4'))
+        self.pool_build_s = time.perf_counter() - t0
+
+    def _advance(self, n):
+        """The host mirrors after n device steps with rollovers: done is T_ITER >= max_steps after the
+        step's increment and a pool row restarts at T_ITER = 0, so iteration wraps at max_steps and
+        episode increases there; no device read."""
+        it = self.iteration
+        first = np.maximum(self.max_steps - it, 1)          # steps to the env's first rollover
+        rolled, rem = n >= first, n - first
+        self.episode += np.where(rolled, 1 + rem // self.max_steps, 0)
+        self.iteration = np.where(rolled, rem % self.max_steps, it + n)
 
     def reset(self, mask=None):
+        if self.reset_pool and self._pool is None:
+            self._build_pool()
+            if mask is None:                # (the envs are in their last pool reset)
+                self.t_obs.copy_(self.torch.from_numpy(self._obs))
+                self._cur = self.t_obs.clone()
+                return self.t_obs.clone()
         obs = super().reset(mask)
         self.t_obs.copy_(self.torch.from_numpy(obs))
         self._cur = self.t_obs.clone()
@@ -465,6 +522,20 @@ class AVRTorchVecEnv(AVRVecEnv):
         # caching allocator cannot hand `a`'s memory to later work before the step has read it)
         self.sim.step_device(a.data_ptr(), self.t_obs.data_ptr(), self.t_rew.data_ptr(), self.t_done.data_ptr(), self.t_info.data_ptr())
         torch.cuda.current_stream(self.dev).wait_stream(self.ext)
+        if self._pool is not None:
+            # the boundary on the device: finished envs take a pool state, t_obs rows become their reset
+            # observations; the terminal ones are in the handle's rows (no host work, no synchronisation)
+            self.sim.rollover_device(self.t_done.data_ptr(), self.t_obs.data_ptr())
+            torch.cuda.current_stream(self.dev).wait_stream(self.ext)
+            dh = self.iteration + 1 >= self.max_steps
+            self._advance(1)
+            obs, rew, done = self.t_obs.clone(), self.t_rew.clone(), self.t_done.bool()
+            info = {'total_force_on_human': self.t_info[:, 0].clone(), 'task_success': self.t_info[:, 1].to(torch.int64),
+                    'action_robot_len': self.L.ACT_DIM, 'action_human_len': 0, 'obs_robot_len': self.L.OBS_DIM, 'obs_human_len': 0}
+            if dh.any():
+                info['terminal_observation'] = torch.where(done[:, None], self._pool[0], obs)
+            self._cur = obs
+            return obs, rew, done, info
         self.iteration += 1
         obs, rew, done = self.t_obs.clone(), self.t_rew.clone(), self.t_done.bool()
         info = {'total_force_on_human': self.t_info[:, 0].clone(), 'task_success': self.t_info[:, 1].to(torch.int64),
@@ -502,14 +573,21 @@ class AVRTorchVecEnv(AVRVecEnv):
         done [n, E] uint8, info [n, E, 2] = {total_force_on_human, task_success}, and reset, the
         [E] bool mask of the envs rolled over after the call (None: none; obs[n] stays their
         terminal observation, the next rollout starts from their reset one).  The tensors are the
-        env's own buffers, one set per rollout length: the next rollout of that length overwrites them."""
+        env's own buffers, one set per rollout length: the next rollout of that length overwrites them.
+
+        With a reset pool (reset_pool=m) n is not capped and nothing synchronises or resets on the
+        host: an env with done[k] set starts its next episode at step k+1 from a pool state, obs[k+1]
+        is its reset observation, reset is done.any(0) (a bool device tensor), and term_obs [E, obs_dim] /
+        term_value [E] (views of the handle's rows) hold the terminal observation of each env's most
+        recent rollover and its value."""
         torch = self.torch
         if self._cur is None:
             raise RuntimeError('rollout_policy: reset() the env first')
         if actor_critic is not None:
             self.set_policy(actor_critic, ob_rms)
         n = int(n)
-        if self.auto_reset:
+        pooled = self._pool is not None
+        if self.auto_reset and not pooled:
             n = min(n, int(self.max_steps - self.iteration.max()))
         if n < 1:
             raise ValueError('rollout_policy: n must be >= 1')
@@ -525,6 +603,13 @@ class AVRTorchVecEnv(AVRVecEnv):
                                        B['obs'].data_ptr(), B['act'].data_ptr(), B['logp'].data_ptr(), B['value'].data_ptr(),
                                        B['rew'].data_ptr(), B['done'].data_ptr(), B['info'].data_ptr())
         torch.cuda.current_stream(self.dev).wait_stream(self.ext)
+        if pooled:
+            # episode boundaries were crossed on the device: obs[k+1] of an env with done[k] is its reset
+            # observation (act[k+1], logp[k+1] belong to it), the terminal one is in term_obs
+            self._advance(n)
+            self.policy_t += n
+            self._cur = B['obs'][n].clone()
+            return dict(B, n=n, reset=B['done'].bool().any(0), term_obs=self._pool[0], term_value=self._pool[1])
         self.iteration += n
         self.policy_t += n
         out = dict(B, n=n, reset=None)

@@ -40,6 +40,11 @@
     int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *d_obs0, int32_t deterministic,    \
                                   float *d_obs, float *d_act, float *d_logp, float *d_value, float *d_rew,          \
                                   uint8_t *d_done, float *d_info);                                                 \
+    int avr_reset_pool_set(avr_sim *s, int32_t n_pool, const float *host_state, const float *host_obs);            \
+    int avr_rollover_enable(avr_sim *s, int32_t on);                                                               \
+    int avr_rollover_device(avr_sim *s, const uint8_t *d_done, float *d_obs);                                      \
+    int avr_rollover_buffers(avr_sim *s, float **d_term_obs, float **d_term_value, int32_t **d_episode);           \
+    int avr_rollover_set_episodes(avr_sim *s, const int32_t *host_episode);                                        \
     int avr_step(avr_sim *s, const float *act, float *obs, float *rew, uint8_t *done, float *info);                \
     int avr_sync(avr_sim *s);                                                                                      \
     int avr_set_profile_buffer(avr_sim *s, void *d_prof);                                                          \
@@ -199,6 +204,11 @@ int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *o0
                               uint8_t *d, float *i) {
     DISPATCH(s, avr_rollout_policy_device(h, t0, n, o0, det, o, a, lp, v, r, d, i));
 }
+int avr_reset_pool_set(avr_sim *s, int32_t n, const float *st, const float *o) { DISPATCH(s, avr_reset_pool_set(h, n, st, o)); }
+int avr_rollover_enable(avr_sim *s, int32_t on) { DISPATCH(s, avr_rollover_enable(h, on)); }
+int avr_rollover_device(avr_sim *s, const uint8_t *d, float *o) { DISPATCH(s, avr_rollover_device(h, d, o)); }
+int avr_rollover_buffers(avr_sim *s, float **to, float **tv, int32_t **ep) { DISPATCH(s, avr_rollover_buffers(h, to, tv, ep)); }
+int avr_rollover_set_episodes(avr_sim *s, const int32_t *ep) { DISPATCH(s, avr_rollover_set_episodes(h, ep)); }
 int avr_substep(avr_sim *s, float dt) { DISPATCH(s, avr_substep(h, dt)); }
 int avr_sync(avr_sim *s) { DISPATCH(s, avr_sync(h)); }
 int avr_kernel_info(avr_sim *s, int32_t *o) { DISPATCH(s, avr_kernel_info(h, o)); }

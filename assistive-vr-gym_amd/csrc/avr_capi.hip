@@ -73,6 +73,14 @@ struct avr_sim {
     // the policy on the device (avr_policy_set): the packed weight block (avr_policy.hip), whose
     // address the rollout graphs' policy nodes hold, and the forward's own log-prob / value rows
     float *d_pol, *d_logp, *d_val;
+    int pol_critic;                        // the installed policy has a critic
+    // device-side episode rollover (avr_reset_pool_set, avr_rollover_*; avr_rollover.hip): the pool
+    // block (header, pool_cap state rows, pool_cap observation rows), whose address the rollout
+    // graphs of the rollover mode hold, and the per-env terminal observation / value / episode
+    // counter rows allocated with it
+    float *d_pool, *d_term_obs, *d_term_val;
+    int *d_episode;
+    int pool_cap, rollover;
 };
 
 // Every entry point runs on the handle's device and restores the caller's current device on
@@ -807,7 +815,14 @@ static hipError_t roll_step(avr_sim *s, int g, hipStream_t st, float *o, float *
     if (el == hipSuccess)
         el = avr_launch_step(&s->km, s->d_km, s->d_state, pr ? s->d_act : nullptr, stacked ? s->d_obs : o, stacked ? s->d_rew : r,
                              stacked ? s->d_done : dn, stacked ? s->d_info : in, nullptr, pr ? MODE_STEP : MODE_STEP_RANDOM, -(g + 1), e0, e1, st, nullptr);
-    if (el == hipSuccess && stacked) el = avr_launch_rollout_copy(ck, s->d_obs, s->d_rew, s->d_done, s->d_info, o, r, dn, in, e0, e1, E, st);
+    // rollover mode: the envs this step finished take their next state from the pool, after the step's
+    // last kernel (BedBathing: the stall kernel, which rewrites rew) -- stacked: in the slot copy's launch
+    if (el == hipSuccess && stacked && s->rollover)
+        el = avr_launch_rollover_copy(ck, s->d_pool, s->cfg.seed, s->cfg.env_offset, s->d_state, s->d_obs, s->d_rew, s->d_done, s->d_info, s->d_term_obs,
+                                      s->d_episode, o, r, dn, in, e0, e1, E, st);
+    else if (el == hipSuccess && stacked) el = avr_launch_rollout_copy(ck, s->d_obs, s->d_rew, s->d_done, s->d_info, o, r, dn, in, e0, e1, E, st);
+    else if (el == hipSuccess && s->rollover)
+        el = avr_launch_rollover(s->d_pool, s->cfg.seed, s->cfg.env_offset, s->d_state, dn, o, s->d_term_obs, s->d_episode, e0, e1, st);
     return el;
 }
 
@@ -912,6 +927,14 @@ static int rollout_per_group(avr_sim *s, int64_t t0, int32_t n, float *o, float 
 }
 
 
+// the rollover of every env with d_done[e] != 0 as one launch on the handle's stream (avr_rollover_device,
+// the direct-loop fallbacks of the rollouts)
+static int rollover_all(avr_sim *s, const uint8_t *d_done, float *d_obs) {
+    HIPCHK(s, avr_launch_rollover(s->d_pool, s->cfg.seed, s->cfg.env_offset, s->d_state, d_done, d_obs, s->d_term_obs, s->d_episode, 0, s->cfg.n_envs,
+                                  s->stream));
+    return 0;
+}
+
 int avr_rollout_random_device(avr_sim *s, int64_t t0, int32_t n, float *d_obs, float *d_rew, uint8_t *d_done, float *d_info, int32_t stacked) {
     CHECK_SIM(s);
     if (t0 < 0 || n < 0) return fail(s, -1, "avr_rollout_random_device: t0 %lld / n %d < 0", (long long)t0, n);
@@ -924,12 +947,14 @@ int avr_rollout_random_device(avr_sim *s, int64_t t0, int32_t n, float *d_obs, f
         for (int k = 0; k < n; k++) {
             const size_t q = stacked ? (size_t)k : 0;
             HIPCHK(s, run_step(s, s->d_state, nullptr, o + q * E * K_OBS_DIM, r + q * E, dn + q * E, in + q * E * AVR_INFO_DIM, nullptr, 1, t0 + k));
+            if (s->rollover && rollover_all(s, dn + q * E, o + q * E * K_OBS_DIM)) return -3;
         }
         return 0;
     }
     // the groups' graphs for these outputs: step outputs straight to the caller's buffers, or
     // (stacked) to the handle's buffers and a copy into slot k
-    const void *key[8] = {o, r, dn, in, (const void *)(size_t)(stacked + 1), nullptr, nullptr, nullptr};
+    // (the rollover mode is part of the key: its graphs hold other nodes)
+    const void *key[8] = {o, r, dn, in, (const void *)(size_t)(stacked + 1 + 8 * s->rollover), nullptr, nullptr, nullptr};
     if (per_group_rollout(s)) return rollout_per_group(s, t0, n, o, r, dn, in, stacked, key, nullptr);
     return rollout_branches(s, t0, n, o, r, dn, in, stacked, key, nullptr);
 }
@@ -987,6 +1012,7 @@ int avr_policy_set(avr_sim *s, const avr_policy_desc *p) {
     // handle's stream); waited for, since the staging vector goes away on return
     HIPCHK(s, hipMemcpyAsync(s->d_pol, w.data(), PW_WORDS * sizeof(float), hipMemcpyHostToDevice, s->stream));
     HIPCHK(s, hipStreamSynchronize(s->stream));
+    s->pol_critic = nc != 0;
     return 0;
 }
 
@@ -1019,6 +1045,7 @@ int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *d_
                                         d_act + k * E * K_ACT_DIM, d_logp ? d_logp + k * E : nullptr, d_value ? d_value + k * E : nullptr, nullptr,
                                         (int)E, flags, 0, (int)E, s->stream));
             HIPCHK(s, run_step(s, s->d_state, s->d_act, s->d_obs, s->d_rew, s->d_done, s->d_info, nullptr, 0, 0));
+            if (s->rollover && rollover_all(s, s->d_done, s->d_obs)) return -3;
             HIPCHK(s, hipMemcpyAsync(d_obs + (k + 1) * OB, s->d_obs, OB * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
             HIPCHK(s, hipMemcpyAsync(d_rew + k * E, s->d_rew, E * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
             HIPCHK(s, hipMemcpyAsync(d_done + k * E, s->d_done, E, hipMemcpyDeviceToDevice, s->stream));
@@ -1028,7 +1055,7 @@ int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *d_
         // the random rollout's graphs with the forward in front of every step; the step's
         // observation goes to slot k + 1, hence the stacked observation array shifted by one slot
         const PolicyRoll pr = {flags, d_act, d_logp, d_value};
-        const void *key[8] = {d_obs, d_rew, d_done, d_info, (const void *)(size_t)(3 + flags), d_act, d_logp, d_value};
+        const void *key[8] = {d_obs, d_rew, d_done, d_info, (const void *)(size_t)(3 + flags + 8 * s->rollover), d_act, d_logp, d_value};
         const int rc = per_group_rollout(s) ? rollout_per_group(s, t0, n, d_obs + OB, d_rew, d_done, d_info, 1, key, &pr)
                                             : rollout_branches(s, t0, n, d_obs + OB, d_rew, d_done, d_info, 1, key, &pr);
         if (rc) return rc;
@@ -1036,6 +1063,72 @@ int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *d_
     if (d_value)       // the bootstrap value of the final observation (the groups are joined by now)
         HIPCHK(s, avr_launch_policy(s->d_pol, s->km.step_t, t0 + n, s->cfg.seed, s->cfg.env_offset, s->d_obs, nullptr, nullptr, s->d_val, nullptr, nullptr,
                                     d_value + (size_t)n * E, nullptr, (int)E, POL_VALUE_ONLY, 0, (int)E, s->stream));
+    if (s->rollover && s->pol_critic)       // V of the terminal observations (each env's most recent rollover)
+        HIPCHK(s, avr_launch_policy(s->d_pol, s->km.step_t, t0 + n, s->cfg.seed, s->cfg.env_offset, s->d_term_obs, nullptr, nullptr, s->d_term_val, nullptr,
+                                    nullptr, nullptr, nullptr, (int)E, POL_VALUE_ONLY, 0, (int)E, s->stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------ device-side episode rollover
+int avr_reset_pool_set(avr_sim *s, int32_t n_pool, const float *host_state, const float *host_obs) {
+    CHECK_SIM(s);
+    if (n_pool < 1) return fail(s, -1, "avr_reset_pool_set: n_pool %d < 1 (avr_rollover_enable(0) switches the rollover off)", (int)n_pool);
+    if (!host_state || !host_obs) return fail(s, -1, "avr_reset_pool_set: host_state and host_obs must be given");
+    const size_t E = (size_t)s->cfg.n_envs;
+    if (!s->d_pool) {
+        // one block: the pool, then the per-env rows (terminal observation, its value, episode counter), zeroed
+        const size_t pw = ROLL_HDR + (size_t)n_pool * (K_STATE_WORDS + K_OBS_DIM), ew = E * (K_OBS_DIM + 2);
+        float *blk = nullptr;
+        HIPCHK(s, hipMalloc(&blk, (pw + ew) * sizeof(float)));
+        s->allocs.push_back(blk);
+        HIPCHK(s, hipMemsetAsync(blk, 0, (pw + ew) * sizeof(float), s->stream));
+        s->d_term_obs = blk + pw; s->d_term_val = s->d_term_obs + E * K_OBS_DIM; s->d_episode = (int *)(s->d_term_val + E);
+        s->pool_cap = n_pool;
+        s->d_pool = blk;
+    }
+    // a larger pool would move the block under the rollout graphs that hold its address: rejected
+    if (n_pool > s->pool_cap)
+        return fail(s, -1, "avr_reset_pool_set: n_pool %d exceeds the pool block's %d rows (sized by the handle's first pool)", (int)n_pool, s->pool_cap);
+    // in stream order after every rollout queued so far (each joins its groups back into the handle's
+    // stream); waited for, since the caller's arrays and the header go away on return
+    const int32_t hdr[ROLL_HDR] = {n_pool, s->pool_cap, 0, 0};
+    HIPCHK(s, hipMemcpyAsync(s->d_pool, hdr, sizeof(hdr), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(s, hipMemcpyAsync(s->d_pool + ROLL_HDR, host_state, (size_t)n_pool * K_STATE_WORDS * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(s, hipMemcpyAsync(s->d_pool + ROLL_HDR + (size_t)s->pool_cap * K_STATE_WORDS, host_obs, (size_t)n_pool * K_OBS_DIM * sizeof(float),
+                             hipMemcpyHostToDevice, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+int avr_rollover_enable(avr_sim *s, int32_t on) {
+    CHECK_SIM(s);
+    if (!s->d_pool) return fail(s, -1, "avr_rollover_enable: no reset pool (call avr_reset_pool_set first)");
+    s->rollover = on ? 1 : 0;
+    return 0;
+}
+
+int avr_rollover_device(avr_sim *s, const uint8_t *d_done, float *d_obs) {
+    CHECK_SIM(s);
+    if (!s->d_pool) return fail(s, -1, "avr_rollover_device: no reset pool (call avr_reset_pool_set first)");
+    if (!d_done || !d_obs) return fail(s, -1, "avr_rollover_device: d_done and d_obs must be given");
+    return rollover_all(s, d_done, d_obs);
+}
+
+int avr_rollover_buffers(avr_sim *s, float **d_term_obs, float **d_term_value, int32_t **d_episode) {
+    CHECK_SIM(s);
+    if (!s->d_pool) return fail(s, -1, "avr_rollover_buffers: no reset pool (call avr_reset_pool_set first)");
+    if (d_term_obs) *d_term_obs = s->d_term_obs;
+    if (d_term_value) *d_term_value = s->d_term_val;
+    if (d_episode) *d_episode = s->d_episode;
+    return 0;
+}
+
+int avr_rollover_set_episodes(avr_sim *s, const int32_t *host_episode) {
+    CHECK_SIM(s);
+    if (!s->d_pool) return fail(s, -1, "avr_rollover_set_episodes: no reset pool (call avr_reset_pool_set first)");
+    if (!host_episode) return fail(s, -1, "avr_rollover_set_episodes: host_episode is NULL");
+    HIPCHK(s, hipMemcpyAsync(s->d_episode, host_episode, (size_t)s->cfg.n_envs * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
     return 0;
 }
 

@@ -877,6 +877,24 @@ int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *d_
     (void)t0; (void)n; (void)d_obs0; (void)deterministic; (void)d_obs; (void)d_act; (void)d_logp; (void)d_value; (void)d_rew; (void)d_done; (void)d_info;
     return fail(s, -1, "policy rollouts: not built for DressingJaco");
 }
+// (the device-side episode rollover rides on those rollout graphs as well, avr_rollover.hip)
+int avr_reset_pool_set(avr_sim *s, int32_t n_pool, const float *host_state, const float *host_obs) {
+    (void)n_pool; (void)host_state; (void)host_obs;
+    return fail(s, -1, "device rollover: not built for DressingJaco");
+}
+int avr_rollover_enable(avr_sim *s, int32_t on) { (void)on; return fail(s, -1, "device rollover: not built for DressingJaco"); }
+int avr_rollover_device(avr_sim *s, const uint8_t *d_done, float *d_obs) {
+    (void)d_done; (void)d_obs;
+    return fail(s, -1, "device rollover: not built for DressingJaco");
+}
+int avr_rollover_buffers(avr_sim *s, float **d_term_obs, float **d_term_value, int32_t **d_episode) {
+    (void)d_term_obs; (void)d_term_value; (void)d_episode;
+    return fail(s, -1, "device rollover: not built for DressingJaco");
+}
+int avr_rollover_set_episodes(avr_sim *s, const int32_t *host_episode) {
+    (void)host_episode;
+    return fail(s, -1, "device rollover: not built for DressingJaco");
+}
 int avr_step(avr_sim *s, const float *act, float *obs, float *rew, uint8_t *done, float *info) {
     CHECK_SIM(s);
     const size_t E = (size_t)s->cfg.n_envs;

@@ -25,5 +25,6 @@ namespace AVR_NS {
 #include "avr_reset_ik.hip"
 #include "avr_base_search.hip"
 #include "avr_policy.hip"
+#include "avr_rollover.hip"
 #include "avr_capi.hip"
 }  // namespace AVR_NS

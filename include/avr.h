@@ -39,7 +39,8 @@ extern "C" {
                                   6: avr_reset_ik self-contact screening (alt4), avr_robot_self_contact;
                                   still 6: avr_policy_set, avr_policy_act_device, avr_rollout_policy_device are new
                                   exports only -- no existing signature or state layout changed, so recordings
-                                  (avr/record.py refuses another ABI number) stay valid */
+                                  (avr/record.py refuses another ABI number) stay valid; avr_reset_pool_set and
+                                  avr_rollover_* likewise */
 #define AVR_FLAGS_FAULT_MASK 0x1f  /* avr_get_flags bits 0-4; bit 5 (EPA budget) is informational */
 
 typedef struct avr_config {
@@ -146,9 +147,57 @@ int avr_policy_act_device(avr_sim *sim, int64_t t, const float *d_obs, int32_t d
  *   d_info[n][n_envs][AVR_INFO_DIM]                                    one slot per step
  *   d_value[n+1][n_envs]          slot k = V(obs slot k) (the last by one value-only launch)
  * d_logp and d_value may be NULL.  No reset inside a rollout: done comes out and the caller resets
- * (as avr_rollout_random_device).  An error before avr_policy_set. */
+ * (as avr_rollout_random_device) -- unless the rollover mode below is on.  An error before avr_policy_set. */
 int avr_rollout_policy_device(avr_sim *sim, int64_t t0, int32_t n, const float *d_obs0, int32_t deterministic, float *d_obs, float *d_act,
                               float *d_logp, float *d_value, float *d_rew, uint8_t *d_done, float *d_info);
+
+/* ---- device-side episode rollover from a reset-state pool (FeedingJaco, ScratchItchPR2, BedBathingPR2;
+ *      DressingJaco: -1) ----
+ * A pool of settled reset states lives on the device; an env that finishes an episode takes its next
+ * initial state from it on the device, inside the rollout's graph replay, with no host work (no
+ * reference counterpart: the reference resets one env on the host, feeding.py:144-331).  The rollover
+ * of env e:
+ *   1. d_term_obs[e] = its d_obs row (the terminal observation);
+ *   2. j = x0 % n_pool, x0 = word 0 of Philox4x32-10 on the counter {env_offset + e, (uint32)episode,
+ *      0x40000000, (uint32)(episode >> 32)} with key (seed lo, seed hi), episode = d_episode[e] before
+ *      the increment (the action stream's counter word 2 is 0 or 1 and the policy noise's has the top bit
+ *      set: this stream shares a counter with neither; avr/_lib.py rollover_index is the host mirror);
+ *   3. the env's state row = pool state j (T_ITER and T_FLAGS come from the pool row, as in a host reset);
+ *   4. its d_obs row = pool observation j;
+ *   5. d_episode[e] += 1.
+ * done, rew and info of the finishing step stay as the step wrote them.  Integer work and copies only.
+ *
+ * avr_reset_pool_set: upload n_pool >= 1 reset states host_state[n_pool][avr_task_state_words] (settled
+ *   states, as avr_get_state returns them after avr_reset / avr_reset_ik) and their reset observations
+ *   host_obs[n_pool][obs_dim] (as the reset wrote them).  The first call allocates the pool's device
+ *   block (n_pool rows) and the per-env rows of avr_rollover_buffers (zeroed); later calls overwrite the
+ *   contents in stream order, and the kernels read n_pool from device memory, so a new pool needs no
+ *   graph re-capture.  A later pool with more rows than the block holds is rejected (the rollout graphs
+ *   hold the block's address); n_pool == 0 is an error (avr_rollover_enable(0) switches the mode off). */
+int avr_reset_pool_set(avr_sim *sim, int32_t n_pool, const float *host_state, const float *host_obs);
+/* avr_rollover_enable: the handle's rollover mode, off by default; an error before avr_reset_pool_set.
+ *   While on, every step of avr_rollout_random_device and avr_rollout_policy_device (both replay forms
+ *   and the direct loop) is followed by the rollover of the envs whose done byte that step set.  In
+ *   stacked rollouts the observation slot of step k then holds, for a rolled env, the reset observation:
+ *   in avr_rollout_policy_device slot k + 1 is what the policy acts on at step k + 1, so act[k + 1] and
+ *   logp[k + 1] belong to obs[k + 1], done[k] = 1 marks the boundary, and the terminal observation is
+ *   in d_term_obs -- of each env's most recent rollover only, when n exceeds an episode.  A non-stacked
+ *   rollout leaves the reset observation in the caller's buffer.  With a critic installed,
+ *   avr_rollout_policy_device ends with one value-only launch over d_term_obs into d_term_value.
+ *   The mode is part of the rollout graphs' key: off and on never replay each other's graphs, and
+ *   switching back and forth re-uses both.  avr_step_device and avr_step_random_device never roll over. */
+int avr_rollover_enable(avr_sim *sim, int32_t on);
+/* avr_rollover_device: the same operation as one call for the per-step API, asynchronous on
+ *   avr_stream(sim): the envs with d_done[e] != 0 roll over and their d_obs[n_envs*obs_dim] rows are
+ *   rewritten (the mode need not be on; the rollouts' direct loop is this call after every step). */
+int avr_rollover_device(avr_sim *sim, const uint8_t *d_done, float *d_obs);
+/* avr_rollover_buffers: device pointers owned by the handle (any may be NULL): d_term_obs[n_envs*obs_dim]
+ *   the terminal observation of each env's most recent rollover (zero until the first), d_term_value
+ *   [n_envs] V of it (avr_rollout_policy_device), d_episode[n_envs] the per-env episode counters. */
+int avr_rollover_buffers(avr_sim *sim, float **d_term_obs, float **d_term_value, int32_t **d_episode);
+/* avr_rollover_set_episodes: set the counters from host_episode[n_envs] (a facade that mixes host
+ *   resets and device rollovers; blocks until done). */
+int avr_rollover_set_episodes(avr_sim *sim, const int32_t *host_episode);
 
 /* One Bullet sub-step of length dt for every env, no task glue (known-answer tests). */
 int avr_substep(avr_sim *sim, float dt);
