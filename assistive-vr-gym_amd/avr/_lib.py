@@ -23,7 +23,9 @@ EXPORTS = [
     'avr_graph_captures', 'avr_robot_self_contact', 'avr_narrowphase_query', 'avr_bb_closest_query',
     'avr_policy_set', 'avr_policy_act_device', 'avr_rollout_policy_device',
     'avr_reset_pool_set', 'avr_rollover_enable', 'avr_rollover_device', 'avr_rollover_buffers', 'avr_rollover_set_episodes',
+    'avr_human_variants_set', 'avr_human_variants', 'avr_human_variant_info', 'avr_narrowphase_query_slots',
 ]
+MAX_HUMAN_VARIANTS = 64      # include/avr.h AVR_MAX_HUMAN_VARIANTS
 FLAGS_FAULT_MASK = 0x1f      # include/avr.h AVR_FLAGS_FAULT_MASK: bits 0-4; bit 5 (EPA budget) is informational
 
 
@@ -40,6 +42,12 @@ class avr_policy_desc(C.Structure):
     ARRAYS = ('ob_mean', 'ob_var', 'a_w1', 'a_b1', 'a_w2', 'a_b2', 'mu_w', 'mu_b', 'logstd', 'c_w1', 'c_b1', 'c_w2', 'c_b2', 'c_w3', 'c_b3')
     _fields_ = [('obs_dim', C.c_int32), ('act_dim', C.c_int32), ('hidden', C.c_int32), ('n_layers', C.c_int32),
                 ('clip_obs', C.c_float), ('eps', C.c_float)] + [(k, C.c_void_p) for k in ARRAYS]
+
+
+class avr_human_variant(C.Structure):
+    """include/avr.h avr_human_variant: one height variant's float32 records (host arrays)."""
+    ARRAYS = ('shape_pose', 'shape_param', 'shape_aabb', 'body_aabb', 'body_threshold', 'hc_jpos', 'hc_inertia', 'bb_targets')
+    _fields_ = [('gender', C.c_int32), ('height', C.c_float), ('n_gshapes', C.c_int32), ('n_hbodies', C.c_int32)] + [(k, C.c_void_p) for k in ARRAYS]
 
 
 _LIB = None
@@ -83,6 +91,12 @@ def load(path=LIB_PATH):
         lib.avr_rollover_device.argtypes = [vp, vp, vp]
         lib.avr_rollover_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         lib.avr_rollover_set_episodes.argtypes = [vp, vp]
+    if hasattr(lib, 'avr_human_variants_set'):      # (absent in experiment builds of older trees)
+        lib.avr_human_variants_set.argtypes = [vp, C.c_int32, vp]
+        lib.avr_human_variants.argtypes = [vp]
+        lib.avr_human_variants.restype = C.c_int32
+        lib.avr_human_variant_info.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        lib.avr_narrowphase_query_slots.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_float, vp]
     lib.avr_sync.argtypes = [vp]
     lib.avr_stream.argtypes = [vp]
     lib.avr_stream.restype = vp
@@ -235,13 +249,19 @@ class Sim:
         self._chk(self.lib.avr_robot_self_contact(self.h, int(len(q)), q.ctypes.data, out.ctypes.data))
         return out
 
-    def narrowphase(self, pairs, poses14, thr=0.02):
+    def narrowphase(self, pairs, poses14, thr=0.02, slots=None):
         """The step's narrowphase per (sa, sb) row of pairs at body poses poses14 (n, 14)
-        (include/avr.h avr_narrowphase_query): (n, 8) {rc, normal on B, point on B, distance}."""
+        (include/avr.h avr_narrowphase_query): (n, 8) {rc, normal on B, point on B, distance}.
+        slots (n,): each query's proportions slot, its shapes from that height variant's tables
+        (avr_narrowphase_query_slots)."""
         p = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         x = np.ascontiguousarray(poses14, np.float32).reshape(len(p), 14)
         out = np.zeros((len(p), 8), np.float32)
-        self._chk(self.lib.avr_narrowphase_query(self.h, int(len(p)), p.ctypes.data, x.ctypes.data, float(thr), out.ctypes.data))
+        if slots is None:
+            self._chk(self.lib.avr_narrowphase_query(self.h, int(len(p)), p.ctypes.data, x.ctypes.data, float(thr), out.ctypes.data))
+        else:
+            sl = np.ascontiguousarray(slots, np.int32).reshape(len(p))
+            self._chk(self.lib.avr_narrowphase_query_slots(self.h, int(len(p)), p.ctypes.data, x.ctypes.data, sl.ctypes.data, float(thr), out.ctypes.data))
         return out
 
     def bb_closest_query(self, cap=-1):
@@ -357,6 +377,36 @@ class Sim:
     def rollover_set_episodes(self, episodes):
         ep = np.ascontiguousarray(episodes, np.int32).reshape(self.n)
         self._chk(self.lib.avr_rollover_set_episodes(self.h, ep.ctypes.data))
+
+    # ---- human height variants (include/avr.h avr_human_variants_set)
+    def human_variants_set(self, records):
+        """Install the handle's height variants: records is a list of model_compiler.
+        human_variant_records dicts (at most MAX_HUMAN_VARIANTS; empty: the base handle again).  A
+        state row selects variant v with the value 2 + v in its T_GENDER word (0 / 1: the handle's
+        base male / female).  Call it before the first state upload."""
+        n = len(records)
+        arr = (avr_human_variant * max(n, 1))()
+        keep = []
+        for i, R in enumerate(records):
+            v = arr[i]
+            v.gender, v.height = int(R['gender']), float(R['height'])
+            v.n_gshapes, v.n_hbodies = len(R['shapes']), len(R['bodies'])
+            for k in avr_human_variant.ARRAYS:
+                a = R.get(k)
+                if a is not None and np.size(a):
+                    a = np.ascontiguousarray(a, np.float32)
+                    keep.append(a)
+                    setattr(v, k, a.ctypes.data)
+        self._chk(self.lib.avr_human_variants_set(self.h, n, C.cast(arr, C.c_void_p) if n else None))
+
+    def human_variants(self):
+        """[(gender 0 / 1, height)] of the loaded variants, as the library holds them."""
+        out = []
+        for v in range(int(self.lib.avr_human_variants(self.h))):
+            g, h = C.c_int32(), C.c_float()
+            self._chk(self.lib.avr_human_variant_info(self.h, v, C.byref(g), C.byref(h)))
+            out.append((int(g.value), float(h.value)))
+        return out
 
     def sync(self):
         self._chk(self.lib.avr_sync(self.h))

@@ -115,6 +115,17 @@ REGISTRY = {
     'DressingJaco-v0':           ('dressing', 'jaco', True),
 }
 
+# The registry's flag counts the ids with a compiled scene and task glue of their own.  Ids that run
+# on another id's build with a reset of their own are built too: id -> the id whose build they use.
+# FeedingJacoNew-v0 is FeedingJaco-v0's scene and kernels with the `new` reset (feeding.py:168-246);
+# the other New ids stay NotImplementedError.
+BUILT_ON = {'FeedingJacoNew-v0': 'FeedingJaco-v0'}
+
+
+def is_built(env_id):
+    return env_id in BUILT_ON or REGISTRY[env_id][2]
+
+
 _SCENES = {}
 _TASK_OF = {'feeding': ABI.TASK_FEEDING, 'scratch_itch': ABI.TASK_SCRATCH, 'bed_bathing': ABI.TASK_BEDBATH, 'dressing': ABI.TASK_DRESSING}
 
@@ -138,6 +149,38 @@ def _scene(task, heights=None):
             A = MC.scene_arrays(ABI.SCENES[_TASK_OF[task]], H)
         _SCENES[key] = (A, ABI.ModelDesc(A))
     return _SCENES[key]
+
+
+def variant_table(human_heights):
+    """The height variants a human_heights argument asks for: None when every entry is a scalar (one
+    rebuilt scene, no variants), else [(gender, height), ...] -- the male list, then the female
+    list; variant v is proportions slot 2 + v (include/avr.h avr_human_variants_set).  Raises
+    ValueError for an unknown gender, a height outside model_compiler.human_heights' [0.3, 1.0] or
+    more than 64 variants."""
+    from . import model_compiler as MC
+    out, any_list = [], False
+    for g in (human_heights or {}):
+        if g not in MC.DEFAULT_HEIGHT:
+            raise ValueError('heights: gender must be male or female, got %r' % (g,))
+    for g in MC.GENDERS:
+        v = (human_heights or {}).get(g)
+        if isinstance(v, (list, tuple, np.ndarray)):
+            any_list = True
+            if not len(v):
+                raise ValueError('human_heights[%r]: an empty list of heights' % g)
+            out += [(g, MC.human_heights({g: float(h)})[g]) for h in v]
+    if not any_list:
+        return None
+    if len(out) > MC.MAX_HUMAN_VARIANTS:
+        raise ValueError('%d height variants: a handle holds at most %d' % (len(out), MC.MAX_HUMAN_VARIANTS))
+    return out
+
+
+def new_height_grid():
+    """FeedingJacoNew-v0's heights: 21 values per gender over [default - 0.1, default + 0.1] in 1 cm
+    steps (the reference draws a continuous height there, feeding.py:170-172)."""
+    from . import model_compiler as MC
+    return {g: [round(MC.DEFAULT_HEIGHT[g] + 0.01 * k, 2) for k in range(-10, 11)] for g in MC.GENDERS}
 
 
 class _Prefetch:
@@ -197,27 +240,53 @@ class AVRVecEnv:
     human_heights: the human's proportions, {gender: hipbone_to_mouth_height} (create_human's
     hmhs = height / 0.6 male, / 0.54 female, human_creation.py:60-63: capsule lengths and joint
     offsets scale by it, BedBathing's wipe targets too, bed_bathing.py:359-370); a gender not
-    named keeps its default.  One set per handle: the reference builds its human at the height
-    the env holds (a replay's setup.pkl, feeding.py:153-156; setup(), feeding.py:20-28).
+    named keeps its default.  A scalar is one rebuilt scene for the handle: the reference builds
+    its human at the height the env holds (a replay's setup.pkl, feeding.py:153-156; setup(),
+    feeding.py:20-28).  A list per gender, {'male': [...], 'female': [...]}, loads the heights as
+    variants of the one handle (include/avr.h avr_human_variants_set, at most 64 in all; FeedingJaco
+    with the 'philox' reset stream): every env then has its own person per episode.
+    height_draw: 'uniform' (default) draws the env's variant among its gender's list per env and
+    episode from the reset's counter-based stream (keyed by global env id and episode, so it does
+    not depend on env_offset sharding); None uses the list's first height.  proportions() returns
+    every env's gender and height.
     """
 
     def __init__(self, env_id='FeedingJaco-v0', n_envs=1, device=0, seed=1001, env_offset=0, auto_reset=True,
                  impairment='random', reset_ik='device', prefetch=True, scratch_attempts=100, scratch_iters=200,
-                 reset_stream='philox', human_heights=None):
+                 reset_stream='philox', human_heights=None, height_draw='uniform'):
         if env_id not in REGISTRY:
             raise KeyError('unknown env id %r' % env_id)
-        task, robot, ok = REGISTRY[env_id]
-        if not ok:
-            raise NotImplementedError('%s: only FeedingJaco-v0, ScratchItchPR2-v0, BedBathingPR2-v0 and DressingJaco-v0 are built (SURVEY 8)' % env_id)
+        task, robot, _ = REGISTRY[env_id]
+        if not is_built(env_id):
+            raise NotImplementedError('%s: only FeedingJaco-v0, FeedingJacoNew-v0, ScratchItchPR2-v0, BedBathingPR2-v0 and DressingJaco-v0 are built (SURVEY 8)' % env_id)
+        if height_draw not in ('uniform', None):
+            raise ValueError("height_draw must be 'uniform' or None, not %r" % (height_draw,))
+        # FeedingJacoNew-v0 (feeding.py:168-246, the `new` branches): a new height per episode from a
+        # 1 cm grid (human_heights overrides it), impairment 'none', waist and head draws, the
+        # human-robot clearance redraw loop
+        self.new = env_id == 'FeedingJacoNew-v0'
+        if self.new:
+            if reset_ik != 'device' or reset_stream != 'philox':
+                raise NotImplementedError("FeedingJacoNew-v0 resets through the device IK and the 'philox' stream")
+            human_heights = new_height_grid() if human_heights is None else human_heights
+            impairment = 'none'
         self.env_id = env_id
         self.n = int(n_envs)
         self.seed = int(seed)
         self.env_offset = int(env_offset)
         self.auto_reset = auto_reset
         self.impairment = impairment
-        self.A, self.md = _scene(task, human_heights)
         from . import model_compiler as MC
-        self.human_heights = MC.human_heights(human_heights)
+        self.variants = variant_table(human_heights)          # None, or [(gender, height)]: slot 2 + v
+        self.height_draw = height_draw
+        self.human_heights_arg = None if human_heights is None else {
+            g: ([float(x) for x in v] if isinstance(v, (list, tuple, np.ndarray)) else (None if v is None else float(v))) for g, v in human_heights.items()}
+        base_heights = {g: v for g, v in (self.human_heights_arg or {}).items() if not isinstance(v, list)}
+        if self.variants and (task != 'feeding' or reset_stream != 'philox'):
+            raise NotImplementedError("%s: lists of heights are built for FeedingJaco's 'philox' resets; the PR2 tasks' host resets take one "
+                                      "height per gender (the library's avr_human_variants_set serves all three rigid tasks)" % env_id)
+        self.A, self.md = _scene(task, base_heights)
+        self.human_heights = MC.human_heights(base_heights)
         self.task = self.md.task
         self.L = self.md.layout
         self.device_ik = self.task == ABI.TASK_FEEDING and reset_ik == 'device'
@@ -227,6 +296,14 @@ class AVRVecEnv:
         self.reset_stream = reset_stream
         self.device = device
         self.sim = _lib.Sim(self.md, self.n, device=device, seed=self.seed, env_offset=self.env_offset)
+        self._variant_ctx = None
+        if self.variants:
+            # the variants' records are rebuilt (about 0.03 s each) and not cached: only their host link
+            # origins stay, the device tables live in the handle
+            recs = [MC.human_variant_records(ABI.SCENES[self.task], g, h, base=base_heights) for g, h in self.variants]
+            self.sim.human_variants_set(recs)
+            self._variant_ctx = dict(slots={g: [2 + v for v, (vg, _) in enumerate(self.variants) if vg == g] for g in MC.GENDERS},
+                                     pos={2 + v: R['human_pos'] for v, R in enumerate(recs)}, draw=height_draw)
         self.observation_space = Box(-1e9, 1e9, (self.L.OBS_DIM,))
         self.action_space = Box(-1.0, 1.0, (self.L.ACT_DIM,))
         self.obs_robot_len, self.obs_human_len = self.L.OBS_DIM, 0
@@ -287,7 +364,9 @@ class AVRVecEnv:
             return RSS.prepare_reset(self.A, self.md, self.seed, ids, genders=self._genders(idx), impairment=self.impairment,
                                      episodes=list(episodes), attempts=self.scratch_attempts)
         out = RS.reset_inputs(self.A, self.md, self.seed, ids, genders=self._genders(idx),
-                              impairment=self.impairment, episodes=list(episodes), stream=self.reset_stream)
+                              impairment=self.impairment, episodes=list(episodes), stream=self.reset_stream, variants=self._variant_ctx)
+        if self.new:        # the `new` human pose: waist and head draws, arms at 0 (redraw 0 of the clearance loop)
+            RS.new_human_rows(self.A, out[0], self.seed, ids, list(episodes), [m['gender'] for m in out[4]], 0, self._variant_ctx)
         # + the self-contact screening's re-drawn target orientations (ik_random_restarts' step_sim)
         return out + (RS.ik_alt_orients(self.seed, ids, list(episodes), out[2].shape[1], self.reset_stream),)
 
@@ -303,7 +382,7 @@ class AVRVecEnv:
             t0 = time.perf_counter()
             key = (tuple(idx.tolist()), tuple(eps.tolist()))
             got = self._prefetch.take(key) if self._prefetch else None
-            Si, t7, init, _, _, alt = got if got is not None else self._inputs(idx, eps)
+            Si, t7, init, _, meta, alt = got if got is not None else self._inputs(idx, eps)
             t1 = time.perf_counter()
             S[idx] = Si
             T = np.zeros((self.n, 7), np.float32)
@@ -315,9 +394,26 @@ class AVRVecEnv:
             Al[..., 3] = 1.0
             Al[idx] = alt
             t2 = time.perf_counter()
-            _, ok = self.sim.reset_ik(mask.astype(np.uint8), S, T, I, keepout8=self._keepout, frames=frames, obs=self._obs, alt=Al)
+            redraws = None
+            if self.new:
+                # the IK first (no settle yet), then the clearance loop on the host with the device
+                # narrowphase at the IK pose, then the settle from the rows it leaves
+                _, ok = self.sim.reset_ik(mask.astype(np.uint8), S, T, I, keepout8=self._keepout, frames=0, obs=self._obs, alt=Al)
+                S = self.sim.get_state()
+                rows = S[idx].astype(np.float64)
+                ids = [self.env_offset + int(i) for i in idx]
+                redraws, self.last_human_robot_distance = RS.new_redraw_loop(
+                    self.A, rows, self.seed, ids, eps, [m['gender'] for m in meta],
+                    lambda Sr, gl: RS.human_robot_distance(self.A, Sr, gl, self.sim.narrowphase), self._variant_ctx)
+                S[idx] = rows
+                self.sim.reset(mask.astype(np.uint8), S, frames, self._obs)
+            else:
+                _, ok = self.sim.reset_ik(mask.astype(np.uint8), S, T, I, keepout8=self._keepout, frames=frames, obs=self._obs, alt=Al)
             self.last_ik_ok = ok
             self.reset_timing = dict(inputs_s=t1 - t0, prefetched=got is not None, pack_s=t2 - t1, device_s=time.perf_counter() - t2)
+            if redraws is not None:
+                self.reset_timing['human_redraws'] = int(redraws.sum())
+                self.reset_timing['human_redraws_max'] = int(redraws.max())
             if self._prefetch:           # speculate: the same envs end their next episode together
                 self._prefetch.start((key[0], tuple((eps + 1).tolist())), idx, eps + 1)
             return
@@ -367,7 +463,7 @@ class AVRVecEnv:
             return
         else:
             Si, _ = RS.batch_reset_states_fast(self.A, self.md, self.seed, ids, genders=self._genders(idx), impairment=self.impairment, episodes=eps,
-                                               stream=self.reset_stream, self_contact=self.sim.robot_self_contact)
+                                               stream=self.reset_stream, self_contact=self.sim.robot_self_contact, variants=self._variant_ctx)
         S[idx] = Si
         self.sim.reset(mask.astype(np.uint8), S, frames, self._obs)
 
@@ -417,6 +513,18 @@ class AVRVecEnv:
 
     def get_state(self):
         return self.sim.get_state()
+
+    def proportions(self, S=None):
+        """(genders, heights) of every env, from the proportions slot in its state row (S: state
+        rows, default the current state): slot 0 / 1 are the handle's base male / female, 2 + v its
+        height variant v."""
+        S = self.get_state() if S is None else np.asarray(S)
+        genders, heights = [], []
+        for s in S[:, self.L.S_TASK + self.L.T_GENDER].astype(int):
+            g, h = (('male', 'female')[s], None) if s < 2 else self.variants[s - 2]
+            genders.append(g)
+            heights.append(self.human_heights[g] if h is None else h)
+        return genders, np.array(heights, float)
 
     def set_state(self, S):
         self.sim.set_state(S)

@@ -1432,6 +1432,67 @@ def scene_arrays(name, heights=None):
     return A
 
 
+GENDERS = ('male', 'female')
+MAX_HUMAN_VARIANTS = 64              # include/avr.h AVR_MAX_HUMAN_VARIANTS
+# what a height variant replaces in a compiled scene: the device tables (fp32 records, per gender) ...
+VARIANT_DEVICE_ARRAYS = ('shape_pose', 'shape_param', 'shape_aabb', 'body_aabb', 'body_threshold', 'hc_jpos', 'hc_inertia', 'bb_targets')
+# ... and the link origins the host resets pose the human with
+VARIANT_HOST_ARRAYS = ('human_male_pos', 'human_female_pos')
+
+
+def human_variant_records(name, gender, height, base=None):
+    """The records of one human height variant of scene `name` (include/avr.h avr_human_variant):
+    what differs from the scene compiled at `base` (human_heights; None: the defaults) when
+    `gender` is rebuilt at hipbone_to_mouth_height `height` and the other gender stays.  Computed in
+    float64 from scene_arrays(name, {gender: height}) and rounded to float32 as ModelDesc /
+    avr_create round a whole scene, so the device values equal a single-height handle's.
+      gender (0 / 1), height, shapes / bodies (the shape and body rows replaced: the gender's
+      shapes, the human bodies), shape_pose [n, 7], shape_param [n, 4], shape_aabb [n, 6],
+      body_aabb [nb, 6] (the gender's box), body_threshold [nb], hc_jpos / hc_inertia [hc_n, 3],
+      bb_targets [160, 4] (BedBathing), and for the host resets human_pos (float64) and the scene
+      itself (arrays)."""
+    if gender not in DEFAULT_HEIGHT:
+        raise ValueError('heights: gender must be male or female, got %r' % (gender,))
+    H = human_heights(base)
+    H[gender] = human_heights({gender: height})[gender]
+    A = scene_arrays(name, H)
+    g = GENDERS.index(gender)
+    sh = np.nonzero(A['shape_gender'] == g)[0].astype(np.int32)
+    hb = np.nonzero(A['body_kind'] == 3)[0].astype(np.int32)
+    hc = int(A['hc_n'])
+
+    def f32(x):
+        return np.ascontiguousarray(x, np.float32)
+
+    R = dict(gender=g, height=float(H[gender]), shapes=sh, bodies=hb,
+             shape_pose=f32(A['shape_pose'][sh]), shape_param=f32(A['shape_param'][sh]), shape_aabb=f32(A['shape_aabb'][sh]),
+             body_aabb=f32(A['body_aabb'].reshape(-1, 2, 6)[hb, g]), body_threshold=f32(A['body_threshold'][hb]),
+             hc_jpos=f32(A['hc_jpos'][g, :hc]), hc_inertia=f32(A['hc_inertia'][g, :hc]),
+             human_pos=np.array(A['human_%s_pos' % gender], float), arrays=A)
+    if 'bb_targets' in A:
+        R['bb_targets'] = f32(A['bb_targets'][g])
+    return R
+
+
+def apply_variant_records(T, R):
+    """The float32 device tables T (a dict of the VARIANT_DEVICE_ARRAYS of a base scene, float32)
+    with variant R's records substituted, as avr_human_variants_set builds the variant's copies."""
+    T = {k: np.array(v, np.float32) for k, v in T.items()}
+    g = R['gender']
+    for k in ('shape_pose', 'shape_param', 'shape_aabb'):
+        T[k][R['shapes']] = R[k]
+    ba = T['body_aabb'].reshape(-1, 2, 6)
+    ba[R['bodies'], g] = R['body_aabb']
+    T['body_aabb'] = ba.reshape(T['body_aabb'].shape)
+    T['body_threshold'][R['bodies']] = R['body_threshold']
+    hc = len(R['hc_jpos'])
+    T['hc_jpos'][g, :hc] = R['hc_jpos']
+    T['hc_inertia'][g, :hc] = R['hc_inertia']
+    if 'bb_targets' in R:
+        T['bb_targets'][g] = R['bb_targets']
+    return T
+
+
 def compile_all(out_dir=DATA_DIR):
     """All compiled scenes, and the asset cache scene_arrays rebuilds them from; returns the
     FeedingJaco one (path, arrays) first."""

@@ -99,9 +99,11 @@ class Recorder:
     def close(self):
         S = self.states[0]
         L = self.env.L
-        genders = ['male' if g == 0 else 'female' for g in S[:, L.S_TASK + L.T_GENDER].astype(int)]
+        # the T_GENDER word is the env's proportions slot (base male / female or a height variant of
+        # the handle): the env maps it to the gender and the height the human was built at
+        genders, heights = self.env.proportions(S)
         setup = dict(env_id=self.env.env_id, robot_type=self.robot_type, gender=genders,
-                     hipbone_to_mouth_height=[0.6 if g == 'male' else 0.54 for g in genders],
+                     hipbone_to_mouth_height=[float(h) for h in heights], human_heights=self.env.human_heights_arg,
                      seed=self.env.seed, env_offset=self.env.env_offset, n_envs=self.env.n, task=int(self.env.task),
                      state_words=int(S.shape[1]), abi=int(ABI.ABI_VERSION), format=FORMAT, snapshot_every='env step')
         with open(os.path.join(self.dir, 'setup.json'), 'w') as f:
@@ -123,7 +125,8 @@ class ReplayEnv:
         self.action_list = np.load(os.path.join(directory, 'actions.npy'), allow_pickle=False)
         self.states = np.load(os.path.join(directory, 'states.npy'), mmap_mode='r', allow_pickle=False)
         self.env = EV.AVRVecEnv(self.setup_info['env_id'], int(self.setup_info['n_envs']), device=device, seed=int(self.setup_info['seed']),
-                                env_offset=int(self.setup_info['env_offset']), auto_reset=False, prefetch=False)
+                                env_offset=int(self.setup_info['env_offset']), auto_reset=False, prefetch=False,
+                                human_heights=self.setup_info.get('human_heights'))     # (the handle's heights and variant lists)
         self.verify = verify
         self.iteration = 0
         self.mismatch = []

@@ -494,12 +494,16 @@ def keepout_box(A, margin=0.05):
     return np.array([c[0], c[1], c[2], 0.0, he[0], he[1], he[2], 0.0])
 
 
-def human_slot_poses_batch(A, genders, QH):
-    """human_slot_poses for many envs at once: genders (N,) str, QH (N, n_joints) -> (N, MAX_HUMAN, 7)."""
+def human_slot_poses_batch(A, genders, QH, slots=None, pos_of=None):
+    """human_slot_poses for many envs at once: genders (N,) str, QH (N, n_joints) -> (N, MAX_HUMAN, 7).
+    slots (N,) with pos_of {slot: link origins}: envs are grouped by proportions slot (a height
+    variant's human_<g>_pos, model_compiler.human_variant_records) instead of by gender; a slot
+    without an entry (0 / 1) uses the scene's own origins."""
     N = len(genders)
     out = np.zeros((N, ABI.MAX_HUMAN, 7))
-    for g in ('male', 'female'):
-        idx = np.array([k for k in range(N) if genders[k] == g], int)
+    groups = [(g, None, np.array([k for k in range(N) if genders[k] == g], int)) for g in ('male', 'female')] if slots is None else \
+        [(genders[np.nonzero(np.asarray(slots) == s)[0][0]], s, np.nonzero(np.asarray(slots) == s)[0]) for s in sorted(set(int(x) for x in slots))]
+    for g, slot, idx in groups:
         if not len(idx):
             continue
         Qg = QH[idx]
@@ -508,7 +512,7 @@ def human_slot_poses_batch(A, genders, QH):
         par = A['human_%s_parent' % g]
         jt = A['human_%s_jtype' % g]
         ax = A['human_%s_axis' % g]
-        pos = A['human_%s_pos' % g]
+        pos = A['human_%s_pos' % g] if slot is None or slot not in (pos_of or {}) else pos_of[slot]
         nl = len(par)
         P = np.zeros((n, nl, 3)); Qq = np.zeros((n, nl, 4))
         bp = np.broadcast_to(base_p, (n, 3)); bq = np.broadcast_to(np.array([0, 0, 0, 1.0]), (n, 4))
@@ -554,14 +558,177 @@ def philox_uniforms(seed, env_ids, episodes, n):
     return out[:, :n]
 
 
-def human_joint_angles_batch(A, gender, head, limit_scale):
-    """human_joint_angles for many envs of one gender: head (N, 3) angles, limit_scale (N,)."""
+# Draws added for the height variants sit far past every index above (PH_INIT + restarts * n_arm is
+# 304 at the default 40 restarts), so every existing id's reset states stay bit for bit:
+PH_VARIANT = 4096            # the env's height variant among its gender's list
+PH_NEW_HUMAN = 4100          # FeedingJacoNew-v0: redraw r's waist (3) and head (3) angles at PH_NEW_HUMAN + 8 r
+
+
+def philox_uniforms_at(seed, env_ids, episodes, j0, n):
+    """Draws j0 .. j0 + n - 1 of the 'philox' reset stream, (N, n) (j0 a multiple of 4)."""
+    from ._lib import philox4x32_10
+    assert j0 % 4 == 0
+    e = np.asarray(env_ids, np.uint64)
+    ep = np.asarray(episodes, np.uint64)
+    seed = int(seed)
+    out = np.zeros((len(e), 4 * ((n + 3) // 4)))
+    for b in range((n + 3) // 4):
+        c = [e, ep, np.full_like(e, j0 // 4 + b), np.full_like(e, 0x5EED)]
+        r = philox4x32_10(c, seed & 0xFFFFFFFF, ((seed >> 32) ^ _PH_TAG) & 0xFFFFFFFF)
+        for k in range(4):
+            out[:, 4 * b + k] = (r[k].astype(np.float64) + 0.5) * (1.0 / 4294967296.0)
+    return out[:, :n]
+
+
+def variant_draw(seed, env_ids, episodes, n_choices):
+    """Index in [0, n_choices) of each env's height variant for the episode, uniform: draw
+    PH_VARIANT of the env's reset stream, a function of (seed, global env id, episode) alone.
+    n_choices: one count for all envs or one per env."""
+    u = philox_uniforms_at(seed, env_ids, episodes, PH_VARIANT, 1)[:, 0]
+    n = np.broadcast_to(np.asarray(n_choices, np.int64), u.shape)
+    return np.minimum((u * n).astype(np.int64), n - 1)
+
+
+def variant_slots(seed, env_ids, episodes, genders, variants):
+    """The proportions slot (the state row's T_GENDER word) of each env: variants =
+    dict(slots={gender: [slot, ...]}, draw='uniform' | None, ...) as AVRVecEnv builds it.  A gender
+    with no variant list keeps its base slot (0 male, 1 female); draw None takes the list's first.
+    variants['assign'] ({global env id: slot}, optional) fixes the slot of the envs it names (a
+    given person per env); the slot must be one of the env's gender's."""
+    out = np.array([0 if g == 'male' else 1 for g in genders], np.int64)
+    cnt = np.array([max(len(variants['slots'].get(g, ())), 1) for g in genders], np.int64)
+    k = variant_draw(seed, env_ids, episodes, cnt) if variants.get('draw') == 'uniform' else np.zeros(len(out), np.int64)
+    assign = variants.get('assign') or {}
+    for i, g in enumerate(genders):
+        lst = variants['slots'].get(g, ())
+        if len(lst):
+            out[i] = lst[k[i]]
+        if int(env_ids[i]) in assign:
+            s = int(assign[int(env_ids[i])])
+            if s not in list(lst) + [0 if g == 'male' else 1]:
+                raise ValueError('env %d: slot %d is not a %s slot of this handle' % (int(env_ids[i]), s, g))
+            out[i] = s
+    return out
+
+
+NEW_REDRAWS = 16             # FeedingJacoNew-v0: bound of the human-robot clearance redraw loop
+
+
+def new_human_rows(A, S, seed, env_ids, episodes, genders, redraw, variants=None):
+    """FeedingJacoNew-v0's human pose of redraw `redraw[k]` of each env (feeding.py:229-235): the six
+    fixed sitting angles, arm joints 0, head joints 25-27 uniform in +-30 deg and waist joints 0-2
+    in +-10 deg, drawn at PH_NEW_HUMAN + 8 redraw of the env's reset stream.  Writes the human slot
+    poses and the mouth target (feeding.py:253-256) of the rows of S in place; the proportions slot
+    is read from the rows.  Returns the joint angles (N, n_joints)."""
+    N = len(env_ids)
+    redraw = np.broadcast_to(np.asarray(redraw, np.int64), (N,))
+    U = np.zeros((N, 6))
+    for r in sorted(set(int(x) for x in redraw)):
+        k = np.nonzero(redraw == r)[0]
+        U[k] = philox_uniforms_at(seed, np.asarray(env_ids)[k], np.asarray(episodes)[k], PH_NEW_HUMAN + 8 * r, 6)
+    waist = np.deg2rad(-10) + np.deg2rad(20) * U[:, 0:3]
+    head = np.deg2rad(-30) + np.deg2rad(60) * U[:, 3:6]
+    n_j = max(len(A['human_male_parent']), len(A['human_female_parent']))
+    QH = np.zeros((N, n_j))
+    for g in ('male', 'female'):
+        idx = np.array([k for k in range(N) if genders[k] == g], int)
+        if len(idx):
+            q = human_joint_angles_batch(A, g, head[idx], np.ones(len(idx)), waist=waist[idx])
+            QH[idx, :q.shape[1]] = q
+    slots = S[:, ABI.S_TASK + ABI.T_GENDER].astype(int)
+    S[:, ABI.S_HUMAN:ABI.S_HUMAN + ABI.MAX_HUMAN * 7] = human_slot_poses_batch(A, genders, QH, slots, (variants or {}).get('pos')).reshape(N, -1)
+    gi = np.array([0 if g == 'male' else 1 for g in genders])
+    hs = ABI.S_HUMAN + 7 * int(A['task_head_slot'])
+    mouth = np.where(gi[:, None] == 0, A['task_mouth_male'][None], A['task_mouth_female'][None])
+    t = ABI.S_TASK + ABI.T_TARGET
+    S[:, t:t + 3] = S[:, hs:hs + 3] + _qrot(S[:, hs + 3:hs + 7], mouth)
+    return QH
+
+
+def new_redraw_loop(A, S, seed, env_ids, episodes, genders, distance, variants=None, max_redraws=NEW_REDRAWS, min_dist=0.01):
+    """FeedingJacoNew-v0's clearance loop (feeding.py:227-240): while the human is closer than
+    min_dist to the robot, redraw the human's joint draws -- per env, at most max_redraws times (the
+    reference's loop is unbounded; an env still too close after the bound keeps its last draw).
+    S: state rows with the robot at its IK pose, rewritten in place; distance(S_rows, genders) ->
+    the rows' minimum human-robot distances (human_robot_distance).  Returns (redraws (N,), the
+    final distances (N,))."""
+    N = len(S)
+    env_ids, episodes = np.asarray(env_ids), np.asarray(episodes)
+    redraws = np.zeros(N, np.int64)
+    dist = np.asarray(distance(S, list(genders)), float).copy()
+    while True:
+        k = np.nonzero((dist < min_dist) & (redraws < max_redraws))[0]
+        if not len(k):
+            return redraws, dist
+        redraws[k] += 1
+        Sk = S[k].copy()
+        gk = [genders[i] for i in k]
+        new_human_rows(A, Sk, seed, env_ids[k], episodes[k], gk, redraws[k], variants)
+        S[k] = Sk
+        dist[k] = distance(Sk, gk)
+
+
+def human_robot_distance(A, S, genders, narrowphase, thr=0.05, chunk=256):
+    """min p.getClosestPoints(human, robot, thr)[8] (feeding.py:238) of every state row of S, thr
+    where no pair is within thr: the human shapes of the row's gender (genders[k]), read from its proportions
+    slot's tables, against the robot's shapes at the row's joints, by the step's narrowphase
+    (narrowphase: _lib.Sim.narrowphase, or any function of (pairs, poses14, thr, slots) -> (n, 8);
+    tests inject one).  Pairs whose bounding spheres are further apart than thr plus a slack that
+    covers any height variant's longer capsules are not asked."""
+    S = np.asarray(S, np.float64)
+    N = len(S)
+    nd = int(A['n_dof'])
+    kind, bidx = A['body_kind'], A['body_index']
+    s0, sc = A['body_shape_start'], A['body_shape_count']
+    rob = [(b, s) for b in np.nonzero(kind == ABI.BODY_ROBOT)[0] for s in range(s0[b], s0[b] + sc[b])]
+    hum = [(b, s) for b in np.nonzero(kind == ABI.BODY_HUMAN)[0] for s in range(s0[b], s0[b] + sc[b])]
+    rad = np.linalg.norm(A['shape_aabb'][:, 3:6], axis=1) + np.linalg.norm(A['shape_aabb'][:, 0:3], axis=1)
+    out = np.full(N, float(thr))
+    slack = 0.25
+    for c0 in range(0, N, chunk):
+        rows = np.arange(c0, min(N, c0 + chunk))
+        Sc = S[rows]
+        CP, CQ, _, _ = robot_fk_batch(A, Sc[:, ABI.S_Q:ABI.S_Q + nd])
+        slots = Sc[:, ABI.S_TASK + ABI.T_GENDER].astype(int)
+        pairs, poses, sl, owner = [], [], [], []
+        rb = np.array([b for b, _ in rob]); rs = np.array([s for _, s in rob])
+        rl = bidx[rb]
+        rpos = CP[:, rl] + _qrot(CQ[:, rl], np.broadcast_to(A['shape_pose'][rs, :3], (len(rows), len(rs), 3)))       # (n, R, 3)
+        for k, e in enumerate(rows):
+            g = 0 if genders[e] == 'male' else 1
+            for hb, hsid in hum:
+                sg = int(A['shape_gender'][hsid])
+                if sg >= 0 and sg != g:
+                    continue
+                hp = Sc[k, ABI.S_HUMAN + 7 * bidx[hb]:ABI.S_HUMAN + 7 * bidx[hb] + 7]
+                hc = hp[:3] + _qrot(hp[3:7], A['shape_pose'][hsid, :3])
+                d = np.linalg.norm(rpos[k] - hc, axis=1) - rad[rs] - rad[hsid]
+                for j in np.nonzero(d < thr + slack)[0]:
+                    pairs.append((hsid, rs[j]))
+                    poses.append(np.concatenate([hp, CP[k, rl[j]], CQ[k, rl[j]]]))
+                    sl.append(slots[k])
+                    owner.append(e)
+        if not pairs:
+            continue
+        res = narrowphase(np.array(pairs, np.int32), np.array(poses, np.float32), thr, np.array(sl, np.int32))
+        owner = np.array(owner)
+        hit = res[:, 0] == 1
+        for e in set(owner[hit].tolist()):
+            out[e] = min(float(thr), float(res[hit & (owner == e), 7].min()))
+    return out
+
+
+def human_joint_angles_batch(A, gender, head, limit_scale, waist=None):
+    """human_joint_angles for many envs of one gender: head (N, 3) angles, limit_scale (N,);
+    waist (N, 3): joints 0-2 (FeedingJacoNew-v0, feeding.py:233; None: 0)."""
     lo0, hi0, scaled, clamp = _human_limits(A, gender)
     N = len(head)
     q = np.zeros((N, len(lo0)))
     for j, ang in [(10, -90), (20, -90), (28, -90), (31, 80), (35, -90), (38, 80)]:
         q[:, j] = np.deg2rad(ang)
     q[:, 25:28] = head
+    if waist is not None:
+        q[:, 0:3] = waist
     ls = np.asarray(limit_scale, float)[:, None]
     lo = np.where(scaled[None], lo0[None] * ls, lo0[None])
     hi = np.where(scaled[None], hi0[None] * ls, hi0[None])
@@ -569,8 +736,9 @@ def human_joint_angles_batch(A, gender, head, limit_scale):
     return np.where(c, np.minimum(np.maximum(q, lo), hi), q)
 
 
-def _draws_philox(A, md, seed, env_ids, genders, impairment, episodes, restarts):
-    """The reset draws of the 'philox' stream, vectorised over envs."""
+def _draws_philox(A, md, seed, env_ids, genders, impairment, episodes, restarts, variants=None):
+    """The reset draws of the 'philox' stream, vectorised over envs.  variants (variant_slots): the
+    envs' height variants are drawn too and the human is posed with each variant's link origins."""
     N = len(env_ids)
     lower, upper = arm_limits(md)
     na = len(md.arm_dofs)
@@ -598,10 +766,12 @@ def _draws_philox(A, md, seed, env_ids, genders, impairment, episodes, restarts)
     bowl = np.array([-0.15, -0.55, 0.75]) + np.concatenate([-0.05 + 0.1 * U[:, PH_BOWL:PH_BOWL + 2], np.zeros((N, 1))], 1)
     tpos = bowl + np.array([0, -0.1, 0.4]) + (-0.05 + 0.1 * U[:, PH_TARGET:PH_TARGET + 3])
     init = lower + (upper - lower) * U[:, PH_INIT:PH_INIT + restarts * na].reshape(N, restarts, na)
-    return gl, il, ls, QH, trem, bowl, tpos, init
+    if variants is None:
+        return gl, il, ls, QH, trem, bowl, tpos, init
+    return gl, il, ls, QH, trem, bowl, tpos, init, variant_slots(seed, env_ids, episodes, gl, variants), variants.get('pos')
 
 
-def reset_inputs(A, md, seed, env_ids, genders=None, impairment='none', episodes=None, restarts=40, vector_fk=True, stream='numpy'):
+def reset_inputs(A, md, seed, env_ids, genders=None, impairment='none', episodes=None, restarts=40, vector_fk=True, stream='numpy', variants=None):
     """Everything FeedingEnv.reset draws, for many envs (feeding.py:144-331 minus the IK): state
     rows without the arm's joints, spoon and food (S, float64), the tool link's IK target
     (target7: position + quaternion), the restarts' starting joints (init, (N, restarts, n_arm))
@@ -611,9 +781,11 @@ def reset_inputs(A, md, seed, env_ids, genders=None, impairment='none', episodes
     vector_fk: human link poses by the batched FK (else the per-env one)."""
     if stream == 'philox':
         return _inputs_from_draws(A, md, *_draws_philox(A, md, seed, list(env_ids), genders, impairment,
-                                                        [0] * len(env_ids) if episodes is None else list(episodes), restarts))
+                                                        [0] * len(env_ids) if episodes is None else list(episodes), restarts, variants))
     if stream != 'numpy':
         raise ValueError('unknown reset stream %r' % stream)
+    if variants is not None:
+        raise ValueError("height variants are drawn from the 'philox' reset stream only")
     env_ids = list(env_ids)
     N = len(env_ids)
     eps = [0] * N if episodes is None else list(episodes)
@@ -676,11 +848,12 @@ def reset_inputs(A, md, seed, env_ids, genders=None, impairment='none', episodes
     return S, target7, init, q0, meta
 
 
-def _inputs_from_draws(A, md, gl, il, ls, QH, trem, bowl, tpos, init):
-    """reset_inputs' state rows from already-drawn values (the 'philox' stream), vectorised."""
+def _inputs_from_draws(A, md, gl, il, ls, QH, trem, bowl, tpos, init, slots=None, pos_of=None):
+    """reset_inputs' state rows from already-drawn values (the 'philox' stream), vectorised.
+    slots: the envs' proportions slots (height variants), written to T_GENDER; meta carries them."""
     N = len(gl)
     S = np.zeros((N, ABI.STATE_WORDS))
-    S[:, ABI.S_HUMAN:ABI.S_HUMAN + ABI.MAX_HUMAN * 7] = human_slot_poses_batch(A, gl, QH).reshape(N, -1)
+    S[:, ABI.S_HUMAN:ABI.S_HUMAN + ABI.MAX_HUMAN * 7] = human_slot_poses_batch(A, gl, QH, slots, pos_of).reshape(N, -1)
     tr = np.array([x == 'tremor' for x in il])
     if tr.any():
         nd = md.n_dof
@@ -696,6 +869,10 @@ def _inputs_from_draws(A, md, gl, il, ls, QH, trem, bowl, tpos, init):
     tq = np.repeat(G.quat_from_euler([np.pi / 2.0, 0, np.pi / 2.0])[None], N, 0)
     target7 = np.concatenate([tpos, tq], 1)
     meta = [dict(gender=gl[k], impairment=il[k], limit_scale=float(ls[k]), bowl_pos=bowl[k], target_pos=tpos[k]) for k in range(N)]
+    if slots is not None:
+        S[:, ABI.S_TASK + ABI.T_GENDER] = slots
+        for k in range(N):
+            meta[k]['slot'] = int(slots[k])
     return S, target7, init, q0, meta
 
 
@@ -748,11 +925,12 @@ def place_tool_bodies(A, S, Q):
     return S
 
 
-def batch_reset_states_fast(A, md, seed, env_ids, genders=None, impairment='none', episodes=None, stream='numpy', self_contact=None):
+def batch_reset_states_fast(A, md, seed, env_ids, genders=None, impairment='none', episodes=None, stream='numpy', self_contact=None, variants=None):
     """Vectorised equivalent of batch_reset_states (same per-env draws and acceptance rules,
     IK batched across envs).  episodes[k] selects the k-th env's episode stream (default 0);
-    stream: reset_inputs' draw stream; self_contact: ik_batch's self-contact screening."""
-    S, target7, init, q0, meta = reset_inputs(A, md, seed, env_ids, genders, impairment, episodes, vector_fk=False, stream=stream)
+    stream: reset_inputs' draw stream; self_contact: ik_batch's self-contact screening;
+    variants: the handle's height variants (variant_slots)."""
+    S, target7, init, q0, meta = reset_inputs(A, md, seed, env_ids, genders, impairment, episodes, vector_fk=False, stream=stream, variants=variants)
     lower, upper = arm_limits(md)
     alt = ik_alt_orients(seed, env_ids, episodes, init.shape[1], stream) if self_contact is not None else None
     Q, ok = ik_batch(A, int(A['task_tool_link']), target7[:, :3], target7[:, 3:], md.arm_dofs, lower, upper, init, q0,

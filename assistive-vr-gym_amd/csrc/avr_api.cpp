@@ -45,6 +45,9 @@
     int avr_rollover_device(avr_sim *s, const uint8_t *d_done, float *d_obs);                                      \
     int avr_rollover_buffers(avr_sim *s, float **d_term_obs, float **d_term_value, int32_t **d_episode);           \
     int avr_rollover_set_episodes(avr_sim *s, const int32_t *host_episode);                                        \
+    int avr_human_variants_set(avr_sim *s, int32_t n_var, const avr_human_variant *v);                             \
+    int32_t avr_human_variants(avr_sim *s);                                                                        \
+    int avr_human_variant_info(avr_sim *s, int32_t v, int32_t *gender, float *height);                             \
     int avr_step(avr_sim *s, const float *act, float *obs, float *rew, uint8_t *done, float *info);                \
     int avr_sync(avr_sim *s);                                                                                      \
     int avr_set_profile_buffer(avr_sim *s, void *d_prof);                                                          \
@@ -61,6 +64,8 @@
     int avr_robot_self_contact(avr_sim *s, int32_t n, const float *q, int32_t *out);                               \
     int avr_narrowphase_query(avr_sim *s, int32_t n, const int32_t *pairs, const float *poses14, float thr,         \
                               float *out8);                                                                        \
+    int avr_narrowphase_query_slots(avr_sim *s, int32_t n, const int32_t *pairs, const float *poses14,              \
+                                    const int32_t *slots, float thr, float *out8);                                 \
     int avr_bb_closest_query(avr_sim *s, int32_t cap, float *out4);                                                \
     int avr_base_search(avr_sim *s, int32_t n, int32_t attempts, const float *base7, const float *rest,            \
                         const float *tstart3, const float *goals9, int32_t iters, float tol, int32_t *best,         \
@@ -205,6 +210,9 @@ int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *o0
     DISPATCH(s, avr_rollout_policy_device(h, t0, n, o0, det, o, a, lp, v, r, d, i));
 }
 int avr_reset_pool_set(avr_sim *s, int32_t n, const float *st, const float *o) { DISPATCH(s, avr_reset_pool_set(h, n, st, o)); }
+int avr_human_variants_set(avr_sim *s, int32_t n, const avr_human_variant *v) { DISPATCH(s, avr_human_variants_set(h, n, v)); }
+int32_t avr_human_variants(avr_sim *s) { DISPATCH(s, avr_human_variants(h)); }
+int avr_human_variant_info(avr_sim *s, int32_t v, int32_t *g, float *ht) { DISPATCH(s, avr_human_variant_info(h, v, g, ht)); }
 int avr_rollover_enable(avr_sim *s, int32_t on) { DISPATCH(s, avr_rollover_enable(h, on)); }
 int avr_rollover_device(avr_sim *s, const uint8_t *d, float *o) { DISPATCH(s, avr_rollover_device(h, d, o)); }
 int avr_rollover_buffers(avr_sim *s, float **to, float **tv, int32_t **ep) { DISPATCH(s, avr_rollover_buffers(h, to, tv, ep)); }
@@ -226,6 +234,9 @@ int avr_reset_ik(avr_sim *s, const uint8_t *m, const float *p, const float *t7, 
 int avr_robot_self_contact(avr_sim *s, int32_t n, const float *q, int32_t *out) { DISPATCH(s, avr_robot_self_contact(h, n, q, out)); }
 int avr_narrowphase_query(avr_sim *s, int32_t n, const int32_t *pairs, const float *poses14, float thr, float *out8) {
     DISPATCH(s, avr_narrowphase_query(h, n, pairs, poses14, thr, out8));
+}
+int avr_narrowphase_query_slots(avr_sim *s, int32_t n, const int32_t *pairs, const float *poses14, const int32_t *slots, float thr, float *out8) {
+    DISPATCH(s, avr_narrowphase_query_slots(h, n, pairs, poses14, slots, thr, out8));
 }
 int avr_bb_closest_query(avr_sim *s, int32_t cap, float *out4) { DISPATCH(s, avr_bb_closest_query(h, cap, out4)); }
 int avr_base_search(avr_sim *s, int32_t n, int32_t a, const float *b7, const float *rest, const float *t3, const float *g9, int32_t it, float tol,

@@ -81,6 +81,13 @@ struct avr_sim {
     float *d_pool, *d_term_obs, *d_term_val;
     int *d_episode;
     int pool_cap, rollover;
+    // human height variants (avr_human_variants_set): the scene's shape genders and body kinds (which
+    // rows a variant's records replace), each loaded variant's gender and height, and whether the
+    // per-variant table blocks (sized for the full capacity) have replaced the base tables
+    std::vector<int> h_shape_gender, h_body_kind;
+    int var_gender[AVR_MAX_HUMAN_VARIANTS];
+    float var_height[AVR_MAX_HUMAN_VARIANTS];
+    int var_blocks;
 };
 
 // Every entry point runs on the handle's device and restores the caller's current device on
@@ -361,6 +368,8 @@ int avr_create(const avr_config *cfg, const avr_model_desc *d, avr_sim **out) {
     if ((r = upload(s, ivec(d->shape_kind, ns), &k.shape_kind))) return r;
     if ((r = upload(s, ivec(d->shape_body, ns), &k.shape_body))) return r;
     if ((r = upload(s, ivec(d->shape_gender, ns), &k.shape_gender))) return r;
+    s->h_shape_gender = ivec(d->shape_gender, ns);
+    s->h_body_kind = ivec(d->body_kind, nb);
     if ((r = upload(s, ivec(d->shape_hull, (size_t)ns * 4), &k.shape_hull))) return r;
     if ((r = upload(s, cvt(d->shape_pose, 0, 7, 8, ns), &k.shape_pose))) return r;
     if ((r = upload(s, cvt(d->shape_param, (size_t)ns * 4), &k.shape_param))) return r;
@@ -689,8 +698,149 @@ int32_t avr_dyn_split(const avr_sim *s) { return s ? s->km.dyn_split : 0; }
 
 int64_t avr_graph_captures(avr_sim *s) { return s ? s->n_captures : -1; }
 
+// ------------------------------------------------------------------ human height variants
+// Every uploaded state row's proportions slot (the T_GENDER word; avr_kernel.hip) must be loaded: 0, 1
+// or 2 + v with v < n_var.  Checked on the host before anything is copied or launched, so a bad slot
+// never reaches a kernel as a table index.
+static int check_slots(avr_sim *s, const char *fn, const float *h, size_t rows, const uint8_t *mask) {
+    if (!h) return fail(s, -1, "%s: host_state is NULL", fn);
+    const int top = 1 + s->km.n_var;
+    for (size_t e = 0; e < rows; e++) {
+        if (mask && !mask[e]) continue;
+        const float w = h[e * K_STATE_WORDS + S_TASK + T_GENDER];
+        if (!(w >= 0.f && w <= (float)top && w == (float)(int)w))
+            return fail(s, -1, "%s: row %zu has proportions slot %g, not loaded: this handle holds slots 0 .. %d (%d height variants)", fn, e, (double)w,
+                        top, s->km.n_var);
+    }
+    return 0;
+}
+
+int32_t avr_human_variants(avr_sim *s) { return s ? s->km.n_var : -1; }
+
+int avr_human_variant_info(avr_sim *s, int32_t v, int32_t *gender, float *height) {
+    CHECK_SIM(s);
+    if (v < 0 || v >= s->km.n_var) return fail(s, -1, "avr_human_variant_info: variant %d of %d", (int)v, s->km.n_var);
+    if (gender) *gender = s->var_gender[v];
+    if (height) *height = s->var_height[v];
+    return 0;
+}
+
+// a table of `words` floats per copy with `base` base copies grows into a block with room for the
+// full variant capacity behind them (the base copies moved device to device, bit for bit)
+static int grow_table(avr_sim *s, const float **p, size_t words, int base) {
+    float *d = nullptr;
+    HIPCHK(s, hipMalloc(&d, (size_t)(base + AVR_MAX_HUMAN_VARIANTS) * words * sizeof(float)));
+    s->allocs.push_back(d);
+    HIPCHK(s, hipMemset(d, 0, (size_t)(base + AVR_MAX_HUMAN_VARIANTS) * words * sizeof(float)));
+    HIPCHK(s, hipMemcpy(d, *p, (size_t)base * words * sizeof(float), hipMemcpyDeviceToDevice));
+    *p = d;
+    return 0;
+}
+
+// copy `copy` of a table: the base copy `from` with the variant's rows written by `edit`, uploaded
+template <class F>
+static int put_copy(avr_sim *s, const float *tab, size_t words, int from, int copy, F edit) {
+    std::vector<float> h(words);
+    HIPCHK(s, hipMemcpy(h.data(), tab + (size_t)from * words, words * sizeof(float), hipMemcpyDeviceToHost));
+    edit(h.data());
+    HIPCHK(s, hipMemcpy((float *)tab + (size_t)copy * words, h.data(), words * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int avr_human_variants_set(avr_sim *s, int32_t n_var, const avr_human_variant *v) {
+    CHECK_SIM(s);
+    KModel &k = s->km;
+    if (n_var < 0 || n_var > AVR_MAX_HUMAN_VARIANTS)
+        return fail(s, -1, "avr_human_variants_set: %d variants (0 .. %d per handle)", (int)n_var, AVR_MAX_HUMAN_VARIANTS);
+    if (n_var > 0 && !v) return fail(s, -1, "avr_human_variants_set: variants must be given");
+    const int ns = k.ns, nb = k.nb, nla = k.nla, nl = k.nl, hc = k.hc_n;
+    std::vector<int> gsh[2], hb;
+    for (int i = 0; i < ns; i++)
+        if (s->h_shape_gender[i] == 0 || s->h_shape_gender[i] == 1) gsh[s->h_shape_gender[i]].push_back(i);
+    for (int b = 0; b < nb; b++)
+        if (s->h_body_kind[b] == AVR_BODY_HUMAN) hb.push_back(b);
+    for (int i = 0; i < n_var; i++) {
+        const avr_human_variant &a = v[i];
+        if (a.gender != 0 && a.gender != 1) return fail(s, -1, "avr_human_variants_set: variant %d: gender %d (0 male, 1 female)", i, (int)a.gender);
+        if (!(a.height > 0.f && a.height < 10.f)) return fail(s, -1, "avr_human_variants_set: variant %d: height %g", i, (double)a.height);
+        if (a.n_gshapes != (int)gsh[a.gender].size() || a.n_hbodies != (int)hb.size())
+            return fail(s, -1, "avr_human_variants_set: variant %d: %d shapes / %d human bodies, the scene has %d / %d", i, (int)a.n_gshapes, (int)a.n_hbodies,
+                        (int)gsh[a.gender].size(), (int)hb.size());
+        if (!a.shape_pose || !a.shape_param || !a.shape_aabb || !a.body_aabb || !a.body_threshold || (hc > 0 && (!a.hc_jpos || !a.hc_inertia)) ||
+            (AVR_TASK == AVR_TASK_BEDBATH && !a.bb_targets))
+            return fail(s, -1, "avr_human_variants_set: variant %d: a record array is NULL", i);
+    }
+    // nothing queued on the handle may still read the tables
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    int r;
+    if (n_var > 0 && !s->var_blocks) {
+        if ((r = grow_table(s, &k.shape_pose, (size_t)ns * 8, 1))) return r;
+        if ((r = grow_table(s, &k.shape_param, (size_t)ns * 4, 1))) return r;
+        if ((r = grow_table(s, &k.shape_aabb, (size_t)ns * 8, 1))) return r;
+        if ((r = grow_table(s, &k.body_aabb, (size_t)nb * 12, 1))) return r;
+        if ((r = grow_table(s, &k.body_threshold, (size_t)nb, 1))) return r;
+        if ((r = grow_table(s, &k.rl_jorig, (size_t)nla * 8, 2))) return r;
+        if ((r = grow_table(s, &k.rl_com, (size_t)nla * 8, 2))) return r;
+        if ((r = grow_table(s, &k.rl_inertia, (size_t)nla * 4, 2))) return r;
+        if ((r = grow_table(s, &k.rl_mass, (size_t)nla, 2))) return r;
+#if AVR_TASK == AVR_TASK_BEDBATH
+        if ((r = grow_table(s, (const float **)&k.bb_tgt, (size_t)AVR_BB_MAX_TARGETS * 4, 2))) return r;
+#endif
+        s->var_blocks = 1;
+    }
+    for (int i = 0; i < n_var; i++) {
+        const avr_human_variant &a = v[i];
+        const int g = a.gender;
+        const std::vector<int> &sh = gsh[g];
+        if ((r = put_copy(s, k.shape_pose, (size_t)ns * 8, 0, 1 + i, [&](float *t) {
+                for (size_t j = 0; j < sh.size(); j++)
+                    for (int q = 0; q < 7; q++) t[8 * sh[j] + q] = a.shape_pose[7 * j + q];
+            }))) return r;
+        if ((r = put_copy(s, k.shape_param, (size_t)ns * 4, 0, 1 + i, [&](float *t) {
+                for (size_t j = 0; j < sh.size(); j++)
+                    for (int q = 0; q < 4; q++) t[4 * sh[j] + q] = a.shape_param[4 * j + q];
+            }))) return r;
+        if ((r = put_copy(s, k.shape_aabb, (size_t)ns * 8, 0, 1 + i, [&](float *t) {
+                for (size_t j = 0; j < sh.size(); j++)
+                    for (int q = 0; q < 3; q++) { t[8 * sh[j] + q] = a.shape_aabb[6 * j + q]; t[8 * sh[j] + 4 + q] = a.shape_aabb[6 * j + 3 + q]; }
+            }))) return r;
+        if ((r = put_copy(s, k.body_aabb, (size_t)nb * 12, 0, 1 + i, [&](float *t) {
+                for (size_t j = 0; j < hb.size(); j++)
+                    for (int q = 0; q < 6; q++) t[12 * hb[j] + 6 * g + q] = a.body_aabb[6 * j + q];
+            }))) return r;
+        if ((r = put_copy(s, k.body_threshold, (size_t)nb, 0, 1 + i, [&](float *t) {
+                for (size_t j = 0; j < hb.size(); j++) t[hb[j]] = a.body_threshold[j];
+            }))) return r;
+        // link tables: the base rows of the variant's gender, the chain's joint origins and inertias replaced
+        if ((r = put_copy(s, k.rl_jorig, (size_t)nla * 8, g, 2 + i, [&](float *t) {
+                for (int c = 0; c < hc; c++)
+                    for (int q = 0; q < 3; q++) t[8 * (nl + c) + q] = a.hc_jpos[3 * c + q];
+            }))) return r;
+        if ((r = put_copy(s, k.rl_com, (size_t)nla * 8, g, 2 + i, [](float *) {}))) return r;
+        if ((r = put_copy(s, k.rl_inertia, (size_t)nla * 4, g, 2 + i, [&](float *t) {
+                for (int c = 0; c < hc; c++)
+                    for (int q = 0; q < 3; q++) t[4 * (nl + c) + q] = a.hc_inertia[3 * c + q];
+            }))) return r;
+        if ((r = put_copy(s, k.rl_mass, (size_t)nla, g, 2 + i, [](float *) {}))) return r;
+#if AVR_TASK == AVR_TASK_BEDBATH
+        if ((r = put_copy(s, (const float *)k.bb_tgt, (size_t)AVR_BB_MAX_TARGETS * 4, g, 2 + i, [&](float *t) {
+                for (int q = 0; q < AVR_BB_MAX_TARGETS * 4; q++) t[q] = a.bb_targets[q];
+            }))) return r;
+#endif
+        s->var_gender[i] = g;
+        s->var_height[i] = a.height;
+    }
+    k.n_var = n_var;
+    k.var_female = 0ull;
+    for (int i = 0; i < n_var; i++)
+        if (s->var_gender[i]) k.var_female |= 1ull << i;
+    HIPCHK(s, hipMemcpy(s->d_km, &s->km, sizeof(KModel), hipMemcpyHostToDevice));
+    return 0;
+}
+
 int avr_set_state(avr_sim *s, const float *h) {
     CHECK_SIM(s);
+    if (int r = check_slots(s, "avr_set_state", h, (size_t)s->cfg.n_envs, nullptr)) return r;
     HIPCHK(s, hipMemcpyAsync(s->d_state, h, (size_t)s->cfg.n_envs * K_STATE_WORDS * sizeof(float), hipMemcpyHostToDevice, s->stream));
     HIPCHK(s, hipStreamSynchronize(s->stream));
     return 0;
@@ -709,6 +859,7 @@ static int upload_masked(avr_sim *s, const uint8_t *mask, const float *h) {
 int avr_set_state_masked(avr_sim *s, const uint8_t *mask, const float *h) {
     CHECK_SIM(s);
     if (!mask) return avr_set_state(s, h);
+    if (int r = check_slots(s, "avr_set_state_masked", h, (size_t)s->cfg.n_envs, mask)) return r;
     if (upload_masked(s, mask, h)) return -2;
     HIPCHK(s, hipStreamSynchronize(s->stream));
     return 0;
@@ -721,6 +872,7 @@ int avr_reset(avr_sim *s, const uint8_t *mask, const float *h, int32_t n_frames,
     if (!mask) { all.assign(E, 1); mask = all.data(); }
     if (!h) return fail(s, -1, "avr_reset: host_state is NULL");
     if (n_frames < 0) return fail(s, -1, "avr_reset: n_frames < 0");
+    if (int r = check_slots(s, "avr_reset", h, E, mask)) return r;
     if (upload_masked(s, mask, h)) return -2;
     HIPCHK(s, run_step(s, s->d_state, nullptr, s->d_obs, s->d_rew, s->d_done, s->d_info, s->d_mask, 2, n_frames));
     if (host_obs) {
@@ -1074,6 +1226,7 @@ int avr_reset_pool_set(avr_sim *s, int32_t n_pool, const float *host_state, cons
     CHECK_SIM(s);
     if (n_pool < 1) return fail(s, -1, "avr_reset_pool_set: n_pool %d < 1 (avr_rollover_enable(0) switches the rollover off)", (int)n_pool);
     if (!host_state || !host_obs) return fail(s, -1, "avr_reset_pool_set: host_state and host_obs must be given");
+    if (int r = check_slots(s, "avr_reset_pool_set", host_state, (size_t)n_pool, nullptr)) return r;
     const size_t E = (size_t)s->cfg.n_envs;
     if (!s->d_pool) {
         // one block: the pool, then the per-env rows (terminal observation, its value, episode counter), zeroed
@@ -1293,6 +1446,7 @@ int avr_reset_ik(avr_sim *s, const uint8_t *mask, const float *h, const float *t
     if (na < 1 || na > 8) return fail(s, -1, "avr_reset_ik: %d arm DoFs (1..8 supported)", na);
     std::vector<uint8_t> all;
     if (!mask) { all.assign(E, 1); mask = all.data(); }
+    if (int r = check_slots(s, "avr_reset_ik", h, E, mask)) return r;
     const size_t nt = E * 7, ni = E * (size_t)restarts * na, nq = alt4 ? E * (size_t)restarts * 4 : 0, need = nt + ni + nq + (E + 3) / 4;
     if (need > s->ikcap) {
         if (s->d_ik) HIPCHK(s, hipFree(s->d_ik));
@@ -1348,22 +1502,37 @@ int avr_robot_self_contact(avr_sim *s, int32_t n, const float *q, int32_t *out) 
 }
 
 // ------------------------------------------------------------------ narrowphase query (test hook)
-int avr_narrowphase_query(avr_sim *s, int32_t n, const int32_t *pairs, const float *poses14, float thr, float *out8) {
-    CHECK_SIM(s);
-    if (n < 0 || (n > 0 && (!pairs || !poses14 || !out8))) return fail(s, -1, "avr_narrowphase_query: n >= 0, pairs, poses14 and out8 must be given");
+static int np_query(avr_sim *s, const char *fn, int32_t n, const int32_t *pairs, const float *poses14, const int32_t *slots, float thr, float *out8) {
+    if (n < 0 || (n > 0 && (!pairs || !poses14 || !out8))) return fail(s, -1, "%s: n >= 0, pairs, poses14 and out8 must be given", fn);
     for (int32_t i = 0; i < 2 * n; i++)
-        if (pairs[i] < 0 || pairs[i] >= s->km.ns) return fail(s, -1, "avr_narrowphase_query: shape %d out of range", (int)pairs[i]);
+        if (pairs[i] < 0 || pairs[i] >= s->km.ns) return fail(s, -1, "%s: shape %d out of range", fn, (int)pairs[i]);
+    if (slots)
+        for (int32_t i = 0; i < n; i++)
+            if (slots[i] < 0 || slots[i] > 1 + s->km.n_var)
+                return fail(s, -1, "%s: query %d has proportions slot %d, not loaded: this handle holds slots 0 .. %d", fn, (int)i, (int)slots[i], 1 + s->km.n_var);
     if (n == 0) return 0;
     struct Buf { void *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } buf;
-    HIPCHK(s, hipMalloc(&buf.p, (size_t)n * (2 * sizeof(int) + 22 * sizeof(float))));
-    int *d_p = (int *)buf.p;
-    float *d_x = (float *)(d_p + 2 * (size_t)n), *d_o = d_x + 14 * (size_t)n;
+    HIPCHK(s, hipMalloc(&buf.p, (size_t)n * (3 * sizeof(int) + 22 * sizeof(float))));
+    int *d_p = (int *)buf.p, *d_s = d_p + 2 * (size_t)n;
+    float *d_x = (float *)(d_s + (size_t)n), *d_o = d_x + 14 * (size_t)n;
     HIPCHK(s, hipMemcpyAsync(d_p, pairs, 2 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    if (slots) HIPCHK(s, hipMemcpyAsync(d_s, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s->stream));
     HIPCHK(s, hipMemcpyAsync(d_x, poses14, 14 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIPCHK(s, avr_launch_np_query(s->d_km, d_p, d_x, thr, d_o, (int)n, s->stream));
+    HIPCHK(s, avr_launch_np_query(s->d_km, d_p, d_x, slots ? d_s : nullptr, thr, d_o, (int)n, s->stream));
     HIPCHK(s, hipMemcpyAsync(out8, d_o, 8 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(s, hipStreamSynchronize(s->stream));
     return 0;
+}
+
+int avr_narrowphase_query(avr_sim *s, int32_t n, const int32_t *pairs, const float *poses14, float thr, float *out8) {
+    CHECK_SIM(s);
+    return np_query(s, "avr_narrowphase_query", n, pairs, poses14, nullptr, thr, out8);
+}
+
+int avr_narrowphase_query_slots(avr_sim *s, int32_t n, const int32_t *pairs, const float *poses14, const int32_t *slots, float thr, float *out8) {
+    CHECK_SIM(s);
+    if (n > 0 && !slots) return fail(s, -1, "avr_narrowphase_query_slots: slots must be given");
+    return np_query(s, "avr_narrowphase_query_slots", n, pairs, poses14, slots, thr, out8);
 }
 
 // ------------------------------------------------------------------ BedBathing closest-distance query (test hook)

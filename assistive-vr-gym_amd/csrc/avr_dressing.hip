@@ -878,6 +878,15 @@ int avr_rollout_policy_device(avr_sim *s, int64_t t0, int32_t n, const float *d_
     return fail(s, -1, "policy rollouts: not built for DressingJaco");
 }
 // (the device-side episode rollover rides on those rollout graphs as well, avr_rollover.hip)
+int avr_human_variants_set(avr_sim *s, int32_t n_var, const avr_human_variant *v) {
+    (void)n_var; (void)v;
+    return fail(s, -1, "avr_human_variants_set: not built for DressingJaco");
+}
+int32_t avr_human_variants(avr_sim *s) { (void)s; return 0; }
+int avr_human_variant_info(avr_sim *s, int32_t v, int32_t *gender, float *height) {
+    (void)v; (void)gender; (void)height;
+    return fail(s, -1, "avr_human_variant_info: not built for DressingJaco");
+}
 int avr_reset_pool_set(avr_sim *s, int32_t n_pool, const float *host_state, const float *host_obs) {
     (void)n_pool; (void)host_state; (void)host_obs;
     return fail(s, -1, "device rollover: not built for DressingJaco");
@@ -962,6 +971,10 @@ int avr_get_flags(avr_sim *s, int32_t *flags) {
 int avr_narrowphase_query(avr_sim *s, int32_t n, const int32_t *pairs, const float *poses14, float thr, float *out8) {
     (void)n; (void)pairs; (void)poses14; (void)thr; (void)out8;
     return fail(s, -1, "avr_narrowphase_query: DressingJaco has no rigid collision model");
+}
+int avr_narrowphase_query_slots(avr_sim *s, int32_t n, const int32_t *pairs, const float *poses14, const int32_t *slots, float thr, float *out8) {
+    (void)n; (void)pairs; (void)poses14; (void)slots; (void)thr; (void)out8;
+    return fail(s, -1, "avr_narrowphase_query_slots: DressingJaco has no rigid collision model");
 }
 int avr_bb_closest_query(avr_sim *s, int32_t cap, float *out4) {
     (void)cap; (void)out4;

@@ -83,12 +83,13 @@ AVR_DI BBForces bb_forces(const KModel &m, EnvLDS &L, BBShared &B, const float *
     SYNC();
     // targets: world position = limb slot frame x the target's limb-frame position
     const int g = L.gender;
+    const int tgo = lslot(L, m) * AVR_BB_MAX_TARGETS;     // the targets of the env's proportions slot (counts: its gender's)
     const int nu = m.bb_ntgt[g][0], nt = nu + m.bb_ntgt[g][1];
     const tf up = ldtf(L.st + S_HUMAN + 7 * m.bb_limb_slot[0]), fo = ldtf(L.st + S_HUMAN + 7 * m.bb_limb_slot[1]);
     for (int k = lane; k < AVR_BB_MAX_TARGETS; k += 64) {
         bool kill = false;
         if (k < nt && bb_alive(L.st, k)) {
-            const float4 t = m.bb_tgt[g * AVR_BB_MAX_TARGETS + k];
+            const float4 t = m.bb_tgt[tgo + k];
             const v3 w = tfpt(k < nu ? up : fo, V(t.x, t.y, t.z));
             for (int q = 0; q < tot; q++)
                 kill |= len(sub(ld3(B.pts[q]), w)) < 0.025f;
@@ -135,6 +136,7 @@ struct BBView { const float *st; int gender; };
 template <bool OVF = false, class LT>
 AVR_DI float bb_closest(const KModel &m, const LT &L, EpaBuf &E, float *ws, int &ns, const int cap = WS_BB_CAP) {
     const int lane = lane_id();
+    const int vso = lvrow(L, m) * m.ns;     // the human's shapes: the env's variant's
     ns = 0;          // stalled pairs so far
     const int tb = m.tool_body, ts0 = gld(m.body_shape_start + tb), nts = gld(m.body_shape_count + tb);
     int hs0 = 1 << 30, hs1 = 0;
@@ -159,7 +161,7 @@ AVR_DI float bb_closest(const KModel &m, const LT &L, EpaBuf &E, float *ws, int 
         }
         if (sa >= 0) {
             const int bb = gld(m.shape_body + sb);
-            const WShape A = make_wshape(m, sa, ttf), Bs = make_wshape(m, sb, ldtf(L.st + S_HUMAN + 7 * gld(m.body_index + bb)));
+            const WShape A = make_wshape(m, sa, ttf), Bs = make_wshape(m, sb, ldtf(L.st + S_HUMAN + 7 * gld(m.body_index + bb)), vso);
             if ((A.nv > SMALL_NV && A.tab < 0) || (Bs.nv > SMALL_NV && Bs.tab < 0)) coop = !OVF;
             else {
                 v3 nB = V(0, 0, 0), pB = V(0, 0, 0);
@@ -187,7 +189,7 @@ AVR_DI float bb_closest(const KModel &m, const LT &L, EpaBuf &E, float *ws, int 
             cm &= cm - 1;
             const int csa = __shfl(sa, l, 64), csb = __shfl(sb, l, 64);
             const int bb = gld(m.shape_body + csb);
-            const WShape A = make_wshape(m, csa, ttf), Bs = make_wshape(m, csb, ldtf(L.st + S_HUMAN + 7 * gld(m.body_index + bb)));
+            const WShape A = make_wshape(m, csa, ttf), Bs = make_wshape(m, csb, ldtf(L.st + S_HUMAN + 7 * gld(m.body_index + bb)), vso);
             v3 nB = V(0, 0, 0), pB = V(0, 0, 0);
             float d = 0.f;
             int nit, nk;
@@ -278,12 +280,13 @@ AVR_DI float bb_stall_min(const KModel &m, EpaBuf &E, const float *gst, float *w
     const int nq = min(ns, cap);
     const tf ttf = ldtf(gst + S_FREE);
     const float thr = m.closest_distance;
+    const int slot = slot_clamp(m, (int)gst[S_TASK + T_GENDER]), vso = slot_vrow(slot) * m.ns;
     float dmin = ws[WS_BB_DMIN];
     for (int k = 0; k < nq; k++) {
         const int key = __float_as_int(ws[WS_BB_PAIRS + k]);
         const int sa = key & 0xffff, sb = key >> 16;
         const int bb = gld(m.shape_body + sb);
-        const WShape A = make_wshape(m, sa, ttf), Bs = make_wshape(m, sb, ldtf(gst + S_HUMAN + 7 * gld(m.body_index + bb)));
+        const WShape A = make_wshape(m, sa, ttf), Bs = make_wshape(m, sb, ldtf(gst + S_HUMAN + 7 * gld(m.body_index + bb)), vso);
         v3 nB = V(0, 0, 0), pB = V(0, 0, 0);
         float d = 0.f;
         int nit, nk;
@@ -293,7 +296,7 @@ AVR_DI float bb_stall_min(const KModel &m, EpaBuf &E, const float *gst, float *w
     }
     if (ns > cap) {
         int n2;
-        dmin = fminf(dmin, bb_closest<true>(m, BBView{gst, (int)gst[S_TASK + T_GENDER]}, E, ws, n2, cap));
+        dmin = fminf(dmin, bb_closest<true>(m, BBView{gst, slot_gender(m, slot)}, E, ws, n2, cap));
     }
     return dmin;
 }

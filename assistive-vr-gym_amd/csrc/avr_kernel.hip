@@ -188,8 +188,23 @@ static_assert(MAXSH % 64 == 0, "shape info staged 64 per pass");
 // follows the robot's links: its root hangs off the static chest slot (parent -2) and its link
 // frames (== COM frames) are published into the human slot poses, where collision and the task
 // glue (getLinkState(human, 27), feeding.py:134,254) read them.
+// Human proportions slot (avr.h avr_human_variants_set): the state's T_GENDER word.  0 / 1 are the
+// handle's base male / female, 2 + v is height variant v, whose gender is bit v of m.var_female.
+// The gendered link tables hold one row set per slot ([2 + n_var][nla]); the shape and body tables
+// one copy per variant behind the base copy ([1 + n_var]: row 0 serves slots 0 and 1).  Every
+// reader clamps the slot into the loaded range, so a stale word never indexes past a table; with no
+// variants loaded the slot is the gender and every offset is 0.
+AVR_DI int slot_clamp(const KModel &m, int s) { return min(max(s, 0), 1 + m.n_var); }
+AVR_DI int slot_gender(const KModel &m, int s) { return s < 2 ? s : (int)((m.var_female >> (s - 2)) & 1ull); }
+AVR_DI int slot_vrow(int s) { return s < 2 ? 0 : s - 1; }
 template <class LT>
-AVR_DI int lgo(const LT &L, const KModel &m) { return L.gender * m.nla; }   // gendered table offset
+AVR_DI int lslot(const LT &L, const KModel &m) { return slot_clamp(m, (int)L.st[S_TASK + T_GENDER]); }
+template <class LT>
+AVR_DI int lvrow(const LT &L, const KModel &m) { return slot_vrow(lslot(L, m)); }
+// the env's table row as the pair kernel left it in the collision scratch (the kernels that see no state)
+AVR_DI int cs_vrow(const KModel &m, const float *cs) { return m.n_var ? min(max(__float_as_int(gld(cs + CS_VROW)), 0), m.n_var) : 0; }
+template <class LT>
+AVR_DI int lgo(const LT &L, const KModel &m) { return lslot(L, m) * m.nla; }   // per-slot link table offset
 
 // robot_fk's joint-frame scratch: a member of EnvLDS's phase union, of PairsLDS's FK struct
 AVR_DI float (*lk_of(EnvLDS &L))[8] { return L.u.lk; }
@@ -632,12 +647,13 @@ struct WShape {
     v3 he;
 };
 
-AVR_DI WShape make_wshape(const KModel &m, int s, tf body) {
+// vso: the env's offset into the per-variant shape tables, table row x m.ns (0: the base copy)
+AVR_DI WShape make_wshape(const KModel &m, int s, tf body, int vso = 0) {
     WShape w;
     w.kind = gld(m.shape_kind + (s));
-    w.t = tfmul(body, gldtf(m.shape_pose + 8 * s));
+    w.t = tfmul(body, gldtf(m.shape_pose + 8 * (s + vso)));
     w.margin = gld(m.shape_margin + (s));
-    const v3 pa = gld3(m.shape_param + 4 * s);
+    const v3 pa = gld3(m.shape_param + 4 * (s + vso));
     if (w.kind == AVR_BOX) w.he = V(fmaxf(pa.x - w.margin, 0.f), fmaxf(pa.y - w.margin, 0.f), fmaxf(pa.z - w.margin, 0.f));
     else if (w.kind == AVR_CAPSULE) w.he = V(pa.x, pa.y, 0.f);
     else w.he = V(pa.x, 0.f, 0.f);
@@ -1552,9 +1568,9 @@ AVR_DI bool overlap(v3 a0, v3 a1, v3 b0, v3 b1) {
     return a0.x <= b1.x && a1.x >= b0.x && a0.y <= b1.y && a1.y >= b0.y && a0.z <= b1.z && a1.z >= b0.z;
 }
 
-AVR_DI void shape_aabb(const KModel &m, int s, tf body, v3 &mn, v3 &mx) {
-    tf t = tfmul(body, gldtf(m.shape_pose + 8 * s));
-    const float *a = m.shape_aabb + 8 * s;
+AVR_DI void shape_aabb(const KModel &m, int s, tf body, v3 &mn, v3 &mx, int vso = 0) {
+    tf t = tfmul(body, gldtf(m.shape_pose + 8 * (s + vso)));
+    const float *a = m.shape_aabb + 8 * (s + vso);
     aabb_of(t, gld3(a), gld3(a + 4), mn, mx);
 }
 
@@ -1737,6 +1753,7 @@ AVR_DI void pair_in(const float *cs, int k, int nsp, PairIn &P) {
 static_assert(K_MAX_CONTACTS % 4 == 0, "the old pool's keys are read four at a time");
 AVR_DI void collide_batch(const KModel &m, EnvLDS &L, const PairIn &in, int k0, int nq, lds_f *oldcp, int nold, float *newcp, int &nnew) {
     const int lane = lane_id();
+    const int vbo = lvrow(L, m) * m.nb;     // the env's offset into the per-variant body tables
     PROF_START(pb);
     int sa = 0, sb = 0, p = 0, ba = 0, bb = 0;
     int rc = 0;
@@ -1759,7 +1776,7 @@ AVR_DI void collide_batch(const KModel &m, EnvLDS &L, const PairIn &in, int k0, 
 #pragma unroll
     for (int k = 0; k < AVR_CP_WORDS; k++) nw.p[k] = 0.f;
     if (lane < nq) {
-        float thr = fminf(gld(m.body_threshold + (ba)), gld(m.body_threshold + (bb)));
+        float thr = fminf(gld(m.body_threshold + (vbo + ba)), gld(m.body_threshold + (vbo + bb)));
         const int key = sa | (sb << 16);
         // the old pool's points of this pair: a bit mask over the pool (keys read four at a time,
         // every read in flight together), then its first AVR_MANIFOLD_POINTS set bits in pool order
@@ -1803,7 +1820,7 @@ AVR_DI void collide_batch(const KModel &m, EnvLDS &L, const PairIn &in, int k0, 
     }
     PROF_STOP(40, pb);
     if (lane < nq) {
-        float thr = fminf(gld(m.body_threshold + (ba)), gld(m.body_threshold + (bb)));
+        float thr = fminf(gld(m.body_threshold + (vbo + ba)), gld(m.body_threshold + (vbo + bb)));
 #endif
         tf ta = ldtf(L.btf[ba]), tb = ldtf(L.btf[bb]);
         if (rc == 1) manifold_add(oldcp, nw, pk, n, sa, sb, p, ta, tb, nB, pB, d, thr);
@@ -1811,7 +1828,7 @@ AVR_DI void collide_batch(const KModel &m, EnvLDS &L, const PairIn &in, int k0, 
     }
     PROF_STOP(41, pb);
     if (lane < nq) {
-        float thr = fminf(gld(m.body_threshold + (ba)), gld(m.body_threshold + (bb)));
+        float thr = fminf(gld(m.body_threshold + (vbo + ba)), gld(m.body_threshold + (vbo + bb)));
         tf ta = ldtf(L.btf[ba]), tb = ldtf(L.btf[bb]);
 #endif
         manifold_refresh(oldcp, nw, pk, n, ta, tb, thr);
@@ -1858,6 +1875,8 @@ template <class LT>
 AVR_DI void collide_pairs(const KModel &m, LT &L, float *cs) {
     const int lane = lane_id();
     const int gender = L.gender;
+    const int vrow = lvrow(L, m);       // (read before the collision scratch overlays the state words)
+    const int vso = vrow * m.ns;
     PROF_START(pt);
     // body transforms + fattened AABBs (one lane per body: nb <= MAXB < 64)
     v3 bmn = V(0, 0, 0), bmx = V(0, 0, 0);
@@ -1865,7 +1884,7 @@ AVR_DI void collide_pairs(const KModel &m, LT &L, float *cs) {
         const int b = lane;
         tf t = body_tf(m, L, b);
         int g = gld(m.body_kind + (b)) == AVR_BODY_HUMAN ? gender : 0;
-        const float *a = m.body_aabb + 12 * b + 6 * g;
+        const float *a = m.body_aabb + 12 * (b + vrow * m.nb) + 6 * g;
         v3 mn, mx;
         aabb_of(t, ld3(a), ld3(a + 3), mn, mx);
         v3 e = V(BT_BROADPHASE_EXPAND, BT_BROADPHASE_EXPAND, BT_BROADPHASE_EXPAND);
@@ -1888,7 +1907,7 @@ AVR_DI void collide_pairs(const KModel &m, LT &L, float *cs) {
         const int s = lane + 64 * q, sc = min(s, m.ns - 1);
         const int c = s < m.ns ? (int)(L.sinfo[sc] & 511) - 1 : -1;
         v3 mn, mx;
-        shape_aabb(m, sc, ldtf(L.btf[gld(m.shape_body + sc)]), mn, mx);
+        shape_aabb(m, sc, ldtf(L.btf[gld(m.shape_body + sc)]), mn, mx, vso);
         if (c >= 0) {
             st3(L.u.c.caabb[c], mn);
             st3(L.u.c.caabb[c] + 3, mx);
@@ -2117,6 +2136,7 @@ AVR_DI void collide_pairs(const KModel &m, LT &L, float *cs) {
         cs[CS_NSP] = __int_as_float(nsp); cs[CS_FLAGS] = __int_as_float(L.flags);
         cs[CS_N0] = __int_as_float(n0); cs[CS_N1] = __int_as_float(n1);
         cs[CS_COOP] = 0.f;
+        cs[CS_VROW] = __int_as_float(vrow);
     }
     PROF_STOP(2, pt);
 }
@@ -2922,7 +2942,7 @@ AVR_DI bool substep_a(const KModel &m, EnvLDS &L, float dt, float *gst, float *w
 #if AVR_TASK == AVR_TASK_FEEDING
 AVR_DI void mouth_target(const KModel &m, EnvLDS &L) {
     tf t = ldtf(L.st + S_HUMAN + 7 * m.head_slot);
-    int g = (int)L.st[S_TASK + T_GENDER];
+    int g = slot_gender(m, lslot(L, m));
     v3 p = tfpt(t, gld3(m.mouth[g]));
     SYNC();
     if (lane_id() == 0) st3(L.st + S_TASK + T_TARGET, p);
@@ -3048,7 +3068,7 @@ AVR_DI void load_state(const KModel &m, LT &L, const float *gst) {
     r2l(L.st, ts, S_CP);
     if (lane == 0) {
         L.flags = 0;
-        L.gender = (int)gst[S_TASK + T_GENDER];
+        L.gender = slot_gender(m, slot_clamp(m, (int)gst[S_TASK + T_GENDER]));
         const bool hd = env_hdyn(m, gst);
         L.nla = hd ? m.nla : m.nl;
         L.nda = hd ? m.nd + m.hc_n : m.nd;
@@ -3083,7 +3103,7 @@ AVR_DI void load_a(const KModel &m, EnvLDS &L, const float *gst, const float *cs
     r2l(L.u.k.ocp, tp, nold * AVR_CP_WORDS);
     if (lane == 0) {
         L.flags = 0;
-        L.gender = (int)L.st[S_TASK + T_GENDER];
+        L.gender = slot_gender(m, lslot(L, m));
         L.nla = nla;
         L.nda = hd ? m.nd + m.hc_n : m.nd;
     }
@@ -3313,12 +3333,13 @@ AVR_DI int2 np_entry(const float *cs, int l) {
     return make_int2(__float_as_int(e.x), __float_as_int(e.y));
 }
 
-AVR_DI void ph_init(const KModel &m, const float *btf, int2 e, PH &P) {
+AVR_DI void ph_init(const KModel &m, const float *btf, int2 e, PH &P, int vrow) {
     const int sa = e.y & 0xffff, sb = e.y >> 16;
     const int ba = (e.x >> 16) & 0xff, bb = (e.x >> 24) & 0xff;
+    const int vbo = vrow * m.nb, vso = vrow * m.ns;
     P.k = e.x & 0xffff;
-    P.thr = fminf(gld(m.body_threshold + (ba)), gld(m.body_threshold + (bb)));
-    const WShape A = make_wshape(m, sa, ldtf(btf + 8 * ba)), B = make_wshape(m, sb, ldtf(btf + 8 * bb));
+    P.thr = fminf(gld(m.body_threshold + (vbo + ba)), gld(m.body_threshold + (vbo + bb)));
+    const WShape A = make_wshape(m, sa, ldtf(btf + 8 * ba), vso), B = make_wshape(m, sb, ldtf(btf + 8 * bb), vso);
     P.sw = A.kind != AVR_SPHERE;
     P.c = sel3(P.sw, B.t.p, A.t.p);
     P.H = selw(P.sw, A, B);
@@ -3416,6 +3437,7 @@ AVR_DI void np_store(float *cs, int k, int rc, v3 nB, v3 pB, float d) {
 #endif
 AVR_DI int np_coop(const KModel &m, float *cs, int n, EpaBuf &E, int rot, int budget) {
     const int lane = lane_id();
+    const int vrow = cs_vrow(m, cs), vbo = vrow * m.nb, vso = vrow * m.ns;
     // the cooperative pairs of each 64-pair chunk, read once (the stores below rewrite CS_RES)
     unsigned long long bm[MAXSP / 64], bd[MAXSP / 64];
     int nco = 0;
@@ -3445,8 +3467,8 @@ AVR_DI int np_coop(const KModel &m, float *cs, int n, EpaBuf &E, int rot, int bu
                 const int key = __float_as_int(gld(cs + CS_PAIRS + 2 * kj)), w = __float_as_int(gld(cs + CS_PAIRS + 2 * kj + 1));
                 const int sa = key & 0xffff, sb = key >> 16;
                 const int ba = (w >> 16) & 0xff, bb = (w >> 24) & 0xff;
-                const float thr = fminf(gld(m.body_threshold + (ba)), gld(m.body_threshold + (bb)));
-                const WShape A = make_wshape(m, sa, ldtf(cs + CS_BTF + 8 * ba)), B = make_wshape(m, sb, ldtf(cs + CS_BTF + 8 * bb));
+                const float thr = fminf(gld(m.body_threshold + (vbo + ba)), gld(m.body_threshold + (vbo + bb)));
+                const WShape A = make_wshape(m, sa, ldtf(cs + CS_BTF + 8 * ba), vso), B = make_wshape(m, sb, ldtf(cs + CS_BTF + 8 * bb), vso);
                 v3 n2 = V(0, 0, 0), p2 = V(0, 0, 0);
                 float d2 = 0.f;
                 int nit, nk;
@@ -3555,7 +3577,7 @@ AVR_DI void np_list(const KModel &m, const unsigned char *__restrict__ mask, int
         PH P;
         float *pcs = nullptr;      // the env of the lane's pair
         bool act = lane < T;
-        if (act) { (void)item(lane, pcs); ph_init(m, btfs[slot_of(lane)], entry(lane), P); }
+        if (act) { (void)item(lane, pcs); ph_init(m, btfs[slot_of(lane)], entry(lane), P, cs_vrow(m, pcs)); }
         int next = 64;
 #ifdef AVR_PROF
         pcount(32, T);
@@ -3577,7 +3599,7 @@ AVR_DI void np_list(const KModel &m, const unsigned char *__restrict__ mask, int
             if (done) {
                 const int j = next + __popcll(dm & ((1ull << lane) - 1ull));
                 act = j < T;
-                if (act) { (void)item(j, pcs); ph_init(m, btfs[slot_of(j)], entry(j), P); }
+                if (act) { (void)item(j, pcs); ph_init(m, btfs[slot_of(j)], entry(j), P, cs_vrow(m, pcs)); }
             }
             next += __popcll(dm);
         }
@@ -3598,8 +3620,9 @@ AVR_DI void np_list(const KModel &m, const unsigned char *__restrict__ mask, int
             const int k = e.x & 0xffff;
             const int sa = e.y & 0xffff, sb = e.y >> 16;
             const int ba = (e.x >> 16) & 0xff, bb = (e.x >> 24) & 0xff;
-            const float thr = fminf(gld(m.body_threshold + (ba)), gld(m.body_threshold + (bb)));
-            const WShape A = make_wshape(m, sa, ldtf(bt + 8 * ba)), B = make_wshape(m, sb, ldtf(bt + 8 * bb));
+            const int vrow = cs_vrow(m, cs), vbo = vrow * m.nb, vso = vrow * m.ns;     // (per lane: the item's env)
+            const float thr = fminf(gld(m.body_threshold + (vbo + ba)), gld(m.body_threshold + (vbo + bb)));
+            const WShape A = make_wshape(m, sa, ldtf(bt + 8 * ba), vso), B = make_wshape(m, sb, ldtf(bt + 8 * bb), vso);
             int rc = 2;
             v3 nB = V(0, 0, 0), pB = V(0, 0, 0);
             float d = 0.f;

@@ -55,6 +55,7 @@ static_assert(MAXD <= 16 * NDL && MAXL <= 32, "DoF slots per lane / 32-bit link 
 #define CS_L0 (CS_ORG + 4 * MAXL)                   // [MAXSP][2] the sphere-hull pairs, ascending: (k | ba << 16 | bb << 24, sa | sb << 16)
 #define CS_L1 (CS_L0 + 2 * MAXSP)                   // [MAXSP][2] the other pairs, ascending, the same entries
 #define CS_COOP (CS_L1 + 2 * MAXSP)                 // nonzero: some pair of this sub-step was left to the coop kernel (rc 2)
+#define CS_VROW (CS_COOP + 1)                       // int bits: the env's row of the per-variant shape / body tables (0: base)
 #define CS_WORDS (CS_COOP + 4)                      // (keeps every env's CS_RES 16-byte aligned)
 // Per-env dynamics hand-over (m.dynho, HO_WORDS floats per env), written by the pair launch's
 // dynamics role and read by kernel a's contact rows when m.dyn_split is set.  The unconstrained
@@ -140,6 +141,11 @@ struct KModel {
     float *cscr;               // per-env collision scratch between the part-A kernels: [n_envs][CS_WORDS]
     unsigned long long *prof;  // diagnostic builds only (AVR_PROF): [n_envs][16] cycle counters
     long long *step_t;         // the step counter of a replayed step graph (take_step reads it when passed t < 0)
+    // human height variants (avr_human_variants_set; slot encoding in avr_kernel.hip): with n_var > 0
+    // rl_jorig / rl_com / rl_inertia / rl_mass are [2 + n_var][nla], bb_tgt [2 + n_var][AVR_BB_MAX_TARGETS],
+    // shape_pose / shape_param / shape_aabb [1 + n_var][ns], body_aabb / body_threshold [1 + n_var][nb]
+    int n_var;
+    unsigned long long var_female;   // bit v: variant v is female
 };
 
 // Optional event log filled by avr_launch_step (per-kernel timing, see avr_kernel_times):

@@ -316,8 +316,10 @@ hipError_t avr_launch_self_contact(const KModel *d_m, const float *state, const 
 // avr_narrowphase_query (test hook): the step's wave-cooperative narrowphase (closed forms, GJK
 // with margins, EPA for penetrating cores) between shapes sa and sb at given body poses, one
 // wave per query -> {rc, normal on B xyz, point on B xyz, distance}
+// slots (avr_narrowphase_query_slots; NULL: the base tables): query q's proportions slot -- its
+// shapes come from that height variant's tables
 __global__ __launch_bounds__(64) void avr_np_query_kernel(const KModel *__restrict__ mp, const int *__restrict__ pairs, const float *__restrict__ poses,
-                                                          float thr, float *__restrict__ out, int n) {
+                                                          const int *__restrict__ slots, float thr, float *__restrict__ out, int n) {
     __shared__ EpaBuf E;
     const int q = blockIdx.x;
     if (q >= n) return;
@@ -326,7 +328,8 @@ __global__ __launch_bounds__(64) void avr_np_query_kernel(const KModel *__restri
     tf ta, tb;
     ta.p = V(pa[0], pa[1], pa[2]); ta.q = Q(pa[3], pa[4], pa[5], pa[6]);
     tb.p = V(pb[0], pb[1], pb[2]); tb.q = Q(pb[3], pb[4], pb[5], pb[6]);
-    const WShape A = make_wshape(m, pairs[2 * q], ta), B = make_wshape(m, pairs[2 * q + 1], tb);
+    const int vso = slots ? slot_vrow(slot_clamp(m, slots[q])) * m.ns : 0;
+    const WShape A = make_wshape(m, pairs[2 * q], ta, vso), B = make_wshape(m, pairs[2 * q + 1], tb, vso);
     v3 nB = V(0, 0, 0), pB = V(0, 0, 0);
     float d = 0.f;
     int nit, nk;
@@ -344,8 +347,8 @@ __global__ __launch_bounds__(64) void avr_np_query_kernel(const KModel *__restri
     }
 }
 
-hipError_t avr_launch_np_query(const KModel *d_m, const int *pairs, const float *poses, float thr, float *out, int n, hipStream_t st) {
+hipError_t avr_launch_np_query(const KModel *d_m, const int *pairs, const float *poses, const int *slots, float thr, float *out, int n, hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(avr_np_query_kernel, dim3(n), dim3(64), 0, st, d_m, pairs, poses, thr, out, n);
+    hipLaunchKernelGGL(avr_np_query_kernel, dim3(n), dim3(64), 0, st, d_m, pairs, poses, slots, thr, out, n);
     return hipGetLastError();
 }

@@ -199,6 +199,49 @@ int avr_rollover_buffers(avr_sim *sim, float **d_term_obs, float **d_term_value,
  *   resets and device rollovers; blocks until done). */
 int avr_rollover_set_episodes(avr_sim *sim, const int32_t *host_episode);
 
+/* ---- human height variants inside one handle (FeedingJaco, ScratchItchPR2, BedBathingPR2; DressingJaco: -1) ----
+ * The reference's *New-v0 ids draw a new hipbone_to_mouth_height at every reset (feeding.py:170-172) and
+ * rebuild the human (human_creation.py); here a handle holds a finite set of height variants and every env
+ * picks one per episode through its state row.  The T_GENDER word of the task block is the env's
+ * proportions slot: 0 and 1 are the handle's base male and female (every state from before stays valid),
+ * 2 + v is variant v.  The word travels with the row, so avr_set_state, recordings, the reset pool and the
+ * device rollover carry the choice with no other copy; the layouts and avr_task_state_words do not change.
+ *
+ * A variant carries its gender and height and the fp32 records that differ from the base scene for that
+ * gender, rounded as avr_create rounds a whole scene compiled at {gender: height} (the other gender at the
+ * handle's own height), so an env at variant v computes bit for bit what the same env computes in a handle
+ * created from that scene:
+ *   shape_pose[n_gshapes][7], shape_param[n_gshapes][4], shape_aabb[n_gshapes][6]
+ *                                     the shapes with shape_gender == gender, ascending shape index
+ *   body_aabb[n_hbodies][6], body_threshold[n_hbodies]
+ *                                     the AVR_BODY_HUMAN bodies, ascending body index (this gender's box)
+ *   hc_jpos[hc_n][3], hc_inertia[hc_n][3]   the articulated human chain's rows (NULL when hc_n == 0)
+ *   bb_targets[AVR_BB_MAX_TARGETS][4] BedBathing's wipe targets of this gender (NULL for the other tasks)
+ * n_gshapes and n_hbodies must equal the handle's own counts (a record compiled for another scene is refused).
+ *
+ * avr_human_variants_set: install n_var <= AVR_MAX_HUMAN_VARIANTS variants (replacing any earlier set;
+ *   n_var = 0, v NULL: the base handle again).  Call it after avr_create and before the first state upload:
+ *   the tables' device block is allocated by the first call with room for the full capacity, so a later
+ *   call moves nothing a captured graph holds, but rows already on the device keep their slots and a
+ *   smaller set leaves the kernels clamping them into the loaded range.
+ * avr_set_state, avr_set_state_masked, avr_reset, avr_reset_ik and avr_reset_pool_set refuse (-1, message
+ *   in avr_last_error, nothing launched or copied) a row whose slot is not 0, 1 or 2 + v with v < n_var.
+ * With no variants loaded every kernel reads the base tables at offset 0, as before. */
+#define AVR_MAX_HUMAN_VARIANTS 64
+typedef struct avr_human_variant {
+    int32_t gender;                 /* 0 male, 1 female                                             */
+    float height;                   /* hipbone_to_mouth_height, m (reported back; not used in the step) */
+    int32_t n_gshapes, n_hbodies;   /* rows in the arrays below                                     */
+    const float *shape_pose, *shape_param, *shape_aabb;
+    const float *body_aabb, *body_threshold;
+    const float *hc_jpos, *hc_inertia;
+    const float *bb_targets;
+} avr_human_variant;
+int avr_human_variants_set(avr_sim *sim, int32_t n_var, const avr_human_variant *v);
+/* Variants loaded (0: none); avr_human_variant_info: the gender and height of variant v (either may be NULL). */
+int32_t avr_human_variants(avr_sim *sim);
+int avr_human_variant_info(avr_sim *sim, int32_t v, int32_t *gender, float *height);
+
 /* One Bullet sub-step of length dt for every env, no task glue (known-answer tests). */
 int avr_substep(avr_sim *sim, float dt);
 
@@ -304,6 +347,12 @@ int avr_robot_self_contact(avr_sim *sim, int32_t n, const float *q, int32_t *out
  *   does: a pair whose fp32 lane GJK stalls with an open duality gap is answered by the
  *   cooperative GJK with the double simplex solve, every other pair by the cooperative fp32 path. */
 int avr_narrowphase_query(avr_sim *sim, int32_t n, const int32_t *pairs, const float *poses14, float thr, float *out8);
+/* avr_narrowphase_query_slots: the same with a proportions slot per query (slots[n]: 0, 1 or 2 + v of a
+ *   loaded height variant, avr_human_variants_set): query i's shapes are read from that variant's tables.
+ *   FeedingJacoNew-v0's reset asks it for p.getClosestPoints(human, robot, 0.05) (feeding.py:238): the
+ *   human shapes of the env's variant against the robot's at the IK pose (avr/reset.py human_robot_distance).
+ *   A slot that is not loaded is refused (-1). */
+int avr_narrowphase_query_slots(avr_sim *sim, int32_t n, const int32_t *pairs, const float *poses14, const int32_t *slots, float thr, float *out8);
 
 /* avr_bb_closest_query (test hook, BedBathingPR2): min p.getClosestPoints(tool, human, 4.0)[8]
  *   (bed_bathing.py:61) of every env's current state, computed by the step's own code in the
