@@ -504,6 +504,11 @@ int avr_create(const avr_config *cfg, const avr_model_desc *d, avr_sim **out) {
     k.dyn_split = K_DYN_ROLE;
     if (const char *ds = getenv("AVR_DYN_SPLIT"))
         if (ds[0] == '0' || ds[0] == '1') k.dyn_split = K_DYN_ROLE && ds[0] == '1';
+    // flat child-pair enumeration in the pair kernel (K_PAIRS_FLAT: the task's default); AVR_PAIRS_FLAT=0|1 overrides
+    // (the same list in the same order either way)
+    k.pairs_flat = K_PAIRS_FLAT;
+    if (const char *pf = getenv("AVR_PAIRS_FLAT"))
+        if ((pf[0] == '0' || pf[0] == '1') && !pf[1]) k.pairs_flat = pf[0] == '1';
     if (E * (size_t)k.rowstride * sizeof(float) >= 0x7fff0000ull) {
         int r = fail(s, -2, "n_envs %d exceeds the row-buffer addressing limit (%d per handle)", cfg->n_envs, (int)(0x7fff0000ull / (k.rowstride * sizeof(float))));
         return r;
@@ -691,6 +696,7 @@ void *avr_state_device_ptr(avr_sim *s) { return s ? (void *)s->d_state : nullptr
 int32_t avr_n_envs(avr_sim *s) { return s ? s->cfg.n_envs : 0; }
 int32_t avr_env_groups(avr_sim *s) { return s ? s->ngroups : 0; }
 int32_t avr_dyn_split(const avr_sim *s) { return s ? s->km.dyn_split : 0; }
+int32_t avr_pairs_flat(const avr_sim *s) { return s ? s->km.pairs_flat : 0; }
 
 #define CHECK_SIM(s)                         \
     if (!(s) || !(s)->d_state) return -1;    \

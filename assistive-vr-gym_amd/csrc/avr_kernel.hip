@@ -100,6 +100,7 @@ struct EnvLDS {
 // LDS of the pair kernel (avr_substep_pairs_kernel), <= 10 KB so that 16 blocks (a 4096-env
 // launch) are resident at once.  The state words and link frames are dead once the body frames
 // exist, so the collision scratch overlays them.
+#define PF_CULL_CAP 1024       // flat pair enumeration: children culled per batch of active pairs (one survivor bit each)
 struct PairsLDS {
     float btf[MAXB][8];
     unsigned short sinfo[MAXSH];   // m.shape_info (13 bits: child index + 1, gender + 1, kind)
@@ -116,7 +117,14 @@ struct PairsLDS {
             struct {                       // collision detection
                 float bmin[MAXB][4], bmax[MAXB][4];
                 unsigned short apair[MAXAP];        // active body pairs (broadphase output, in pair order)
-                unsigned short candA[128], candB[128];   // children of A (B) whose AABB meets B's (A's) body AABB
+                union {
+                    struct { unsigned short candA[128], candB[128]; };   // children of A (B) whose AABB meets B's (A's) body AABB
+                    struct {                        // flat enumeration (m.pairs_flat), per batch of active pairs:
+                        unsigned long long surv[PF_CULL_CAP / 64];   // the culled children that survive, one bit each
+                        int iinc[64];               // inclusive prefix of the pairs' item counts
+                        unsigned short cinc[64];    // inclusive prefix of the pairs' culled child counts
+                    };
+                };
                 float caabb[MAXCC][6];     // world AABBs of the non-static shapes (min3, max3)
             } c;
         } u;
@@ -1967,7 +1975,172 @@ AVR_DI void collide_pairs(const KModel &m, LT &L, float *cs) {
     float grcpB = 1.f;
     int n0 = 0, n1 = 0;                             // sphere-hull / other pairs
     int gbab = 0;                                   // the compound pair's bodies (ba | bb << 8)
+    // append in lane order; the restated pipeline keeps at most MAXSP shape pairs per
+    // sub-step (flag 8)
+    auto append = [&](bool act, int sa, int sb, int q, int ia, int ib, int bab) __attribute__((always_inline)) {
+        int tot;
+        int pre = ballot_prefix(act, &tot);
+        const int kq = nsp + pre;
+        const bool ok = act && kq < MAXSP;
+        if (ok) {
+            cs[CS_PAIRS + 2 * kq] = __int_as_float(sa | (sb << 16));
+            cs[CS_PAIRS + 2 * kq + 1] = __int_as_float(q | bab << 16);
+        }
+        // the narrowphase kernel's two work lists (pair indices, ascending)
+        const bool sh = ok && sphere_hull(ia, ib);
+        int t0, t1;
+        const int p0 = ballot_prefix(sh, &t0), p1 = ballot_prefix(ok && !sh, &t1);
+        // (entries carry the shape and body indices, so the narrowphase reads no pair record)
+        if (ok) {
+            const int l = sh ? CS_L0 + 2 * (n0 + p0) : CS_L1 + 2 * (n1 + p1);
+            *(float2 *)(cs + l) = make_float2(__int_as_float(kq | bab << 16), __int_as_float(sa | (sb << 16)));
+        }
+        n0 += t0;
+        n1 += t1;
+        nsp += tot;
+    };
+    if (m.pairs_flat) {
+        // Flat enumeration (the same list in the same order): the active pairs are taken in batches
+        // of up to 64 consecutive ones, lane <-> pair.  Per batch, one pass over the concatenated
+        // children of all its culled pairs (a survivor bit each; a batch ends early where they
+        // would exceed PF_CULL_CAP), the pairs' item counts and their prefix, then one pass over
+        // the concatenated items, every lane mapping its index back to (pair, i, j) -- instead
+        // of a setup trip, two culling loops and item rounds of its own for every compound pair.
+        auto scan = [&](int v) __attribute__((always_inline)) {                    // inclusive prefix over the lanes
+            for (int o = 1; o < 64; o <<= 1) {
+                const int y = __shfl_up(v, o, 64);
+                if (lane >= o) v += y;
+            }
+            return v;
+        };
+        // first index whose (non-decreasing) inclusive prefix exceeds x; x is below the last entry
+        auto owner = [&](auto *inc, int x) __attribute__((always_inline)) {
+            int lo = 0;
+#pragma unroll
+            for (int s = 32; s; s >>= 1)
+                if ((int)inc[lo + s - 1] <= x) lo += s;
+            return lo;
+        };
+        // survivors among the children [a, b) of the batch's concatenation
+        auto surv_count = [&](int a, int b) __attribute__((always_inline)) {
+            int n = 0;
+            for (int w = a >> 6; w <= (b - 1) >> 6 && a < b; w++) {
+                unsigned long long x = L.u.c.surv[w];
+                if (w == a >> 6) x &= ~0ull << (a & 63);
+                if (w == (b - 1) >> 6) x &= ~0ull >> (63 - ((b - 1) & 63));
+                n += __popcll(x);
+            }
+            return n;
+        };
+        // the r-th survivor at or after child a (it exists), as an offset from a
+        auto surv_select = [&](int a, int r) __attribute__((always_inline)) {
+            int w = a >> 6;
+            unsigned long long x = L.u.c.surv[w] & (~0ull << (a & 63));
+            for (int c = __popcll(x); r >= c && w < PF_CULL_CAP / 64 - 1; c = __popcll(x)) { r -= c; x = L.u.c.surv[++w]; }
+            int pos = 0;
+#pragma unroll
+            for (int s = 32; s; s >>= 1) {
+                const int c = __popcll(x & (((1ull << s) - 1ull) << pos));
+                if (r >= c) { r -= c; pos += s; }
+            }
+            return 64 * w + pos - a;
+        };
+        for (int k0 = 0; k0 < nap;) {
+            SYNC();                                 // the previous batch's reads of the prefix arrays and survivor bits are done
+            const int kk = k0 + lane;
+            int4 rec;
+            {
+                // record of active pair kk: slot kk / 64 (k / 64 or the next) of lane kk % 64
+                const int s0 = k0 >> 6;
+                const int4 lo = s0 == 0 ? rq0 : s0 == 1 ? rq1 : s0 == 2 ? rq2 : rq3;
+                const int4 hi = s0 == 0 ? rq1 : s0 == 1 ? rq2 : rq3;
+                const int src = kk & 63;
+                const bool up = (kk >> 6) != s0;
+                const int4 a = make_int4(__shfl(lo.x, src), __shfl(lo.y, src), __shfl(lo.z, src), __shfl(lo.w, src));
+                const int4 b = make_int4(__shfl(hi.x, src), __shfl(hi.y, src), __shfl(hi.z, src), __shfl(hi.w, src));
+                rec = kk < nap ? (up ? b : a) : make_int4(0, 0, 0, 0);
+            }
+            const bool one = rec.w & 2;
+            const int na = rec.y >> 16, nb = rec.z >> 16;
+            // (the direct pairs -- bare ones, a single child against at most 64 -- skip the cull as in the loop below)
+            const bool cull = k0 + lane < nap && !one && !(rec.w & 1) && na * nb > 1 && !((na == 1 || nb == 1) && na * nb <= 64);
+            const int cinc = scan(cull ? na + nb : 0);
+            const int nbat = __popcll(__ballot(k0 + lane < nap && cinc <= PF_CULL_CAP));     // (>= 1: a pair has at most 256 children)
+            const bool mine = lane < nbat;
+            const int cpre = cinc - (cull ? na + nb : 0);
+            const int CH = __shfl(cinc, nbat - 1);
+            L.u.c.cinc[lane] = (unsigned short)cinc;
+            SYNC();
+#ifdef AVR_PROF
+            if (lane == 0) { L.prof[43]++; L.prof[44] += (CH + 63) / 64; L.prof[45] += CH; }
+#endif
+            for (int base = 0; base < CH; base += 64) {
+                const int c = min(base + lane, CH - 1);
+                const int o = owner(L.u.c.cinc, c);
+                const int ox = __shfl(rec.x, o), oy = __shfl(rec.y, o), oz = __shfl(rec.z, o);
+                const int loc = c - __shfl(cpre, o), ona = oy >> 16;
+                const bool sideB = loc >= ona;      // a child of B, tested against body A's fattened AABB
+                const int s = sideB ? (oz & 0xffff) + loc - ona : (oy & 0xffff) + loc;
+                const int ob = sideB ? ox & 0xffff : ox >> 16;
+                const int info = L.sinfo[s];
+                bool a = false;
+                if (base + lane < CH && info_enabled(info, gender)) {
+                    v3 c0, c1;
+                    child_aabb(m, L, s, info, c0, c1);
+                    a = overlap(c0, c1, ld3(L.u.c.bmin[ob]), ld3(L.u.c.bmax[ob]));
+                }
+                const unsigned long long sm = __ballot(a);
+                if (lane == 0) L.u.c.surv[base >> 6] = sm;
+            }
+            SYNC();
+            int ncA = na, ncB = nb;
+            if (cull && mine) { ncA = surv_count(cpre, cpre + na); ncB = surv_count(cpre + na, cpre + na + nb); }
+            const int cnt = !mine ? 0 : one ? 1 : ncA * ncB;
+            const float rcpB = 1.f / (float)max(ncB, 1);     // (once per pair, as the loop below has it)
+            const int iinc = scan(cnt);
+            const int IT = __shfl(iinc, 63);
+            L.u.c.iinc[lane] = iinc;
+            SYNC();
+#ifdef AVR_PROF
+            if (lane == 0) L.prof[4] += IT;
+#endif
+            for (int base = 0; base < IT; base += 64) {
+#ifdef AVR_PROF
+                if (lane == 0) L.prof[43]++;
+#endif
+                const int it = min(base + lane, IT - 1);
+                const int o = owner(L.u.c.iinc, it);
+                const int ox = __shfl(rec.x, o), oy = __shfl(rec.y, o), oz = __shfl(rec.z, o), ow = __shfl(rec.w, o);
+                const int t = it - (__shfl(iinc, o) - __shfl(cnt, o));
+                const int oncB = __shfl(ncB, o), ocpre = __shfl(cpre, o);
+                const bool ocull = __shfl((int)cull, o);
+                const int i = (int)(((float)t + 0.5f) * __shfl(rcpB, o));     // exact: t < 2^14, 1 <= ncB <= 128 (avr_create rejects a body of more shapes)
+                const int j = t - i * oncB;
+                int sa = (oy & 0xffff) + i, sb = (oz & 0xffff) + j;
+                if (ocull) {
+                    sa = (oy & 0xffff) + surv_select(ocpre, i);
+                    sb = (oz & 0xffff) + surv_select(ocpre + (oy >> 16), j);
+                }
+                const int ia = L.sinfo[sa], ib = L.sinfo[sb];
+                bool act = false;
+                if (base + lane < IT && info_enabled(ia, gender) && info_enabled(ib, gender)) {
+                    if (ow & 1) act = true;
+                    else {
+                        v3 a0, a1, b0, b1;
+                        child_aabb(m, L, sa, ia, a0, a1);
+                        child_aabb(m, L, sb, ib, b0, b1);
+                        act = overlap(a0, a1, b0, b1);
+                    }
+                }
+                append(act, sa, sb, L.u.c.apair[k0 + o], ia, ib, (ox & 0xffff) | (ox >> 16) << 8);
+            }
+            k0 += nbat;
+        }
+    } else
     for (;;) {
+#ifdef AVR_PROF     // loop trips (43), the cull's rounds of 64 children (44) and the children it tests (45)
+        if (lane == 0) L.prof[43]++;
+#endif
         bool act = false, last = false;
         int sa = 0, sb = 0, q = gp, ia = 0, ib = 0, bab = gbab;
         if (gbase < gn) {                           // the compound pair in progress
@@ -2055,6 +2228,9 @@ AVR_DI void collide_pairs(const KModel &m, LT &L, float *cs) {
                 gcull = !gbare && na * nb > 1 && !((na == 1 || nb == 1) && na * nb <= 64);
                 int ncA = na, ncB = nb;
                 if (gcull) {
+#ifdef AVR_PROF
+                    if (lane == 0) { L.prof[44] += (na + 63) / 64 + (nb + 63) / 64; L.prof[45] += na + nb; }
+#endif
                     const v3 bAmn = ld3(L.u.c.bmin[ba]), bAmx = ld3(L.u.c.bmax[ba]);
                     const v3 bBmn = ld3(L.u.c.bmin[bb]), bBmx = ld3(L.u.c.bmax[bb]);
                     ncA = 0;
@@ -2104,28 +2280,7 @@ AVR_DI void collide_pairs(const KModel &m, LT &L, float *cs) {
                 continue;
             }
         } else last = true;
-        // append in lane order; the restated pipeline keeps at most MAXSP shape pairs per
-        // sub-step (flag 8)
-        int tot;
-        int pre = ballot_prefix(act, &tot);
-        const int kq = nsp + pre;
-        const bool ok = act && kq < MAXSP;
-        if (ok) {
-            cs[CS_PAIRS + 2 * kq] = __int_as_float(sa | (sb << 16));
-            cs[CS_PAIRS + 2 * kq + 1] = __int_as_float(q | bab << 16);
-        }
-        // the narrowphase kernel's two work lists (pair indices, ascending)
-        const bool sh = ok && sphere_hull(ia, ib);
-        int t0, t1;
-        const int p0 = ballot_prefix(sh, &t0), p1 = ballot_prefix(ok && !sh, &t1);
-        // (entries carry the shape and body indices, so the narrowphase reads no pair record)
-        if (ok) {
-            const int l = sh ? CS_L0 + 2 * (n0 + p0) : CS_L1 + 2 * (n1 + p1);
-            *(float2 *)(cs + l) = make_float2(__int_as_float(kq | bab << 16), __int_as_float(sa | (sb << 16)));
-        }
-        n0 += t0;
-        n1 += t1;
-        nsp += tot;
+        append(act, sa, sb, q, ia, ib, bab);
         if (last) break;
     }
     if (nsp > MAXSP) { if (lane == 0) L.flags |= 8; nsp = MAXSP; }
@@ -3143,7 +3298,9 @@ template <class LT>
 AVR_DI void prof_flush(const KModel &m, LT &L, int env) {
 #ifdef AVR_PROF
     SYNC();
-    if (m.prof && lane_id() < AVR_PROF_SLOTS) m.prof[(size_t)env * AVR_PROF_SLOTS + lane_id()] += L.prof[lane_id()];
+    // (atomic: the pair launch's two roles flush into the same env's row, and end at about the same time
+    // since the flat enumeration -- a plain += lost 1.6 % of the pair role's counts)
+    if (m.prof && lane_id() < AVR_PROF_SLOTS && L.prof[lane_id()]) atomicAdd(m.prof + (size_t)env * AVR_PROF_SLOTS + lane_id(), L.prof[lane_id()]);
 #else
     (void)m; (void)L; (void)env;
 #endif

@@ -136,6 +136,8 @@ struct KModel {
     int b4_global;             // diagnostic (AVR_B4_GLOBAL=1): part B reads every row from global memory
     int dyn_split;             // the pair launch runs the dynamics role (AVR_DYN_SPLIT; per-task default): unconstrained
                                // velocities and non-contact rows there, kernel a keeps the manifold update and contact rows
+    int pairs_flat;            // the pair kernel enumerates the child shape pairs in flat passes over all active pairs
+                               // (AVR_PAIRS_FLAT=0|1; per-task default K_PAIRS_FLAT), else one compound pair at a time
     float *dynho;              // per-env dynamics hand-over between the dynamics role and kernel a: [n_envs][HO_WORDS]
     float *ws;                 // per-env workspace between sub-step kernels: [n_envs][128]
     float *cscr;               // per-env collision scratch between the part-A kernels: [n_envs][CS_WORDS]

@@ -258,6 +258,10 @@ int32_t avr_env_groups(avr_sim *sim);
  * default, AVR_DYN_SPLIT=0|1 in the environment at avr_create overrides), else 0.  Results do not
  * depend on it.  No reference counterpart (diagnostic). */
 int32_t avr_dyn_split(const avr_sim *sim);
+/* 1 when the pair kernel enumerates the child shape pairs in flat passes over all active body pairs
+ * (the task's default, AVR_PAIRS_FLAT=0|1 in the environment at avr_create overrides), else 0.
+ * The pair list is the same set in the same order either way.  No reference counterpart (diagnostic). */
+int32_t avr_pairs_flat(const avr_sim *sim);
 /* Graph captures made by this handle so far (each distinct step key captures once; a few keys
  * are cached).  No reference counterpart (diagnostic). */
 int64_t avr_graph_captures(avr_sim *sim);

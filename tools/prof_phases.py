@@ -27,9 +27,9 @@ sim.set_state(S.astype(np.float32)); sim.settle(100 if TASK == 0 else 0)
 names = ['fk', 'bodies+broad', 'childpairs', 'narrow+mf', '#culleditems', '#xcd-mismatch', 'dyn', 'nc_rows', 'c_rows', 'solve', 'integrate', '#cooppairs', 'task', 'collide', '#shapepairs', '#bodypairs', ' lane-narrow', ' coop', ' manifold', '#coop sph-hull', '#coop hull-hull', '#coop other', '#coop bighull', '-',
          ' M entries', ' cholesky', ' M^-1 cols', ' bias (RNEA)', '#coop GJK it', '#coop cycles', '#coop max cyc', '-',
          '#np sph-hull', '#np other', '#np refill trips', '#np ph_steps', '#np GJK it', '#np GJK it max', '#np GJK pairs', '#np closed form',
-         '  mf match', '  mf add', '  mf refresh', '-', '-', '-', '-', '-']
+         '  mf match', '  mf add', '  mf refresh', '#pair loop trips', '#pair cull rounds', '#pair cull children', '-', '-']
 for t in range(int(os.environ.get('PROF_STEPS', '3'))):
-    prof.zero_()
+    prof.zero_(); torch.cuda.synchronize()      # (the handle's streams are not ordered after torch's: zero before the step starts)
     t0 = time.time(); sim.step(_lib.random_actions(1001, np.arange(N), t)); el = time.time() - t0
     p = prof.cpu().numpy().reshape(N, SLOTS).astype(np.float64)
     tot = p[:, [0, 13, 6, 7, 8, 9, 10, 12]].sum(1).mean()   # (coop part) is inside narrow+mf
@@ -41,6 +41,18 @@ for t in range(int(os.environ.get('PROF_STEPS', '3'))):
             print('  %-13s per env-step mean %.1f (per substep %.1f), max %.0f' % (nm, p[:, k].mean(), p[:, k].mean() / 10, p[:, k].max()))
             continue
         print('  %-13s %6.2f%%  mean %.3g  max %.3g' % (nm, 100 * p[:, k].mean() / tot, p[:, k].mean(), p[:, k].max()))
+if os.environ.get('PROF_JSON'):
+    # the pair kernel's phases and counters of the last step, per env and sub-step (mean over envs)
+    import json
+    nsub = 10 if TASK == 0 else 5
+    keep = {0: 'fk cycles', 1: 'bodies+broad cycles', 2: 'childpairs cycles', 4: 'items', 14: 'shape pairs', 15: 'body pairs',
+            43: 'loop trips', 44: 'cull rounds', 45: 'cull children'}
+    rec = {v: p[:, k].mean() / nsub for k, v in keep.items()}
+    rec['max per env (loop trips + cull rounds)'] = (p[:, 43] + p[:, 44]).max() / nsub
+    rec['flat rounds'] = float(np.ceil(rec['cull children'] / 64) + np.ceil(rec['items'] / 64) + 1)
+    rec['serial rounds over flat rounds'] = (rec['loop trips'] + rec['cull rounds']) / rec['flat rounds']
+    rec['childpairs share of the pair block'] = rec['childpairs cycles'] / (rec['fk cycles'] + rec['bodies+broad cycles'] + rec['childpairs cycles'])
+    json.dump(dict(what='tools/prof_phases.py %d, AVR_PROF build, step %d, per env and sub-step' % (N, t), **rec), open(os.environ['PROF_JSON'], 'w'), indent=1)
 St = sim.get_state()
 print('ncp mean', St[:, L.S_TASK + L.T_NCP].mean(), 'flags', np.unique(St[:, L.S_TASK + L.T_FLAGS]))
 # the envs with the slowest contact-row phase: their contact count and robot endpoints (last step)
