@@ -3956,11 +3956,34 @@ AVR_DI f4v bld3(rsrc_t r, int o) {
 // contact header and a zero block, then the four groups' regions, packed:
 //   impulses [n_rows + 2 null slots] | active-contact list [n_c] | contact records [3 n_c][16]
 //   | robot parts of robot-contact rows [n_rob - n_nc][32]
-// (the last two only when the block's four envs fit).
+// (the last two only when the block's four envs fit; B4_ADDR below adds null slots, null list
+// entries and null headers to these regions).
 #ifndef B4_LDSW
 #define B4_LDSW 10240    // LDS words per block
 #endif
 AVR_DI int al4(int x) { return (x + 3) & ~3; }
+
+// Row addresses of the LDS row sources without validity tests (-DB4_ADDR=0: the selects of the
+// global sources, set(R, valid, ...), in the LDS sources too).  A group's LDS regions are laid out
+// so that the step after its last valid one lands on a null row by construction:
+//   impulses: non-contact rows [n_nc] | (B4_NC_LDS) a null slot | torsional rows [3 n_t] | one
+//     (friction 1, friction 2, normal) triple per contact [3 n_c] | a null triple
+//   records: normal [n_c][16] | a null header [4] | friction units | torsional units |
+//     (every row staged) non-contact [n_nc][RWC] | a null non-contact header [8] | robot parts
+// A flat sweep's step j addresses index min(j, a) of its rows (a = 0 once the group has converged:
+// the base moves to the null row).  An active-list entry is the unit's record address (low half)
+// and its impulse triple's address (high half), and entry t of a list of t units is a null unit
+// (the null record of the zero head, the null triple): the friction sweep reads entry min(u, t).
+// A torsional row's entry is two words, (record | impulse slot << 16, its contact's normal
+// impulse): the normal impulses do not change between the normal sweep and the next iteration.
+// The global sources keep their layout (impulses: non-contact | normal | friction | torsional | 2
+// null slots) and their selects.
+#ifndef B4_ADDR
+#define B4_ADDR 1
+#endif
+#define B4_NP (B4_ADDR && B4_NC_LDS ? 1 : 0)     // null impulse slot after the non-contact rows
+AVR_DI unsigned lds_addr(const __attribute__((address_space(3))) void *p) { return (unsigned)(size_t)p; }
+AVR_DI __attribute__((address_space(3))) float *lds_at(unsigned a) { return (__attribute__((address_space(3))) float *)(size_t)a; }
 
 // this lane's part of a row from the row's ownership mask (2 bits per free body: 1 endpoint A,
 // 2 endpoint B, 0 none).  Lanes sl >= MAXF own no free body and read bits 30-31, which every
@@ -3982,7 +4005,7 @@ static_assert(2 * MAXF <= CI_SLOT && MAXNC + K_CROWS * K_MAX_CONTACTS < (1 << (3
 struct NcRow { int o; lds_f *ip; f4v h0, h1; float imp; f2v j0, j1, j2; rv_t r; };   // h1: lo, hi, residual limit
 struct NcSrc {
     typedef NcRow Row;
-    static constexpr bool robot_parts = true;
+    static constexpr bool robot_parts = true, addr = false;
     rsrc_t rs;
     int eo, ro;                // this env's records / robot parts (byte offsets)
     lds_f *ip0, *nullip;       // impulse slots: row 0, null rows
@@ -4009,7 +4032,7 @@ struct NcSrc {
 typedef __attribute__((address_space(3))) char lds_c;
 struct NcLds {
     typedef NcRow Row;
-    static constexpr bool robot_parts = true;
+    static constexpr bool robot_parts = true, addr = B4_ADDR != 0;
     lds_c *blk;
     int eo;                    // row 0's record address + 8 (bytes)
     unsigned rob;              // robot part of the row with slot + 1 = s: rob + ROBW 4 s (bytes, this lane's DoFs)
@@ -4039,12 +4062,13 @@ struct CRowL { unsigned wb; lds_f *ip; f4v h; float imp; f2v j0, j1, j2; rv_t r;
 template <bool RC>             // RC: the block has robot contacts (otherwise no contact row has a robot part)
 struct CLds {
     typedef CRowL Row;
-    static constexpr bool robot_parts = RC;
+    static constexpr bool robot_parts = RC, addr = B4_ADDR != 0;
     lds_c *blk;
     unsigned cn, cf;           // normal record 0 / friction unit 0 of this group, - 8 (bytes)
     unsigned rob;              // robot part of the row with slot + 1 = s: rob + 128 s (bytes, this lane's DoF)
-    lds_f *ipn, *ipf, *nullip; // impulse slots: normal row 0, friction unit 0, null rows
-    unsigned ct;               // (K_TORSION) torsional unit 0 of this group, - 8 (bytes)
+    lds_f *ipn, *ipf, *nullip; // impulse slots: normal row 0, friction unit 0, null rows (B4_ADDR: contact c's triple at ipf + 3 c,
+                               // its normal slot ipn + 3 c = ipf + 3 c + 2; the null triple at nullip = ipf + 3 n_c)
+    unsigned ct;              // (K_TORSION) torsional unit 0 of this group, - 8 (bytes)
     lds_f *ipt;                // (K_TORSION) impulse slot of torsional row 0
     AVR_DI void set(Row &R, bool v, unsigned wb, lds_f *ip) const { R.wb = v ? wb : LNB_NULL; R.ip = v ? ip : nullip; }
     AVR_DI void hdr(Row &R) const { R.h = *(const lds_f4 *)(blk + R.wb + 8); R.imp = *R.ip; }
@@ -4080,7 +4104,7 @@ struct CLds {
 struct CRowG { int o; lds_f *ip; f4v h; float imp; f2v j0, j1, j2; rv_t r; };
 struct CGlb {
     typedef CRowG Row;
-    static constexpr bool robot_parts = true;
+    static constexpr bool robot_parts = true, addr = false;
     rsrc_t rs;
     int cn, cf;                // normal record 0 / friction unit 0 of this env (byte offsets)
     int rob;                   // robot part of the row with slot + 1 = s: rob + 128 s (this lane's DoF)
@@ -4278,7 +4302,15 @@ AVR_DI int pgs4(const KModel &m, const NS &ns, const CS &cs, lds_i *list, lds_i 
     d.rq = d.rq2 = 0.f; d.vx = d.vy = d.vz = d.wx = d.wy = d.wz = 0.f;
 #endif
     // normal rows in contact order: record j at cn + 64 j, impulse slot ipn + j
-    auto at_n = [&](CR &R, int j) { cs.set(R, j < n_c, cs.cn + CRW * 4 * j, cs.ipn + j); };
+    // (B4_ADDR: index min(j, rows) from a base that puts the null record and the null triple at
+    // index rows)
+    auto at_n = [&](CR &R, int j) {
+        if constexpr (CS::addr) {
+            const unsigned k = (unsigned)min(j, n_c);
+            R.wb = cs.cn + CRW * 4 * k;
+            R.ip = (lds_f *)((lds_c *)cs.ipn + __umul24(k, 12u));
+        } else cs.set(R, j < n_c, cs.cn + CRW * 4 * j, cs.ipn + j);
+    };
     // warm start (normal rows, contact order): delta = cached impulse x warm-start factor, which
     // is also the rows' starting impulse
     sweep4<DC, true>(cs, nc_max, at_n, [&](const CR &R) { (void)go4<CS::robot_parts>(R, d, 0.f, R.h.y, R.h.z, R.imp, R.imp); });
@@ -4296,20 +4328,42 @@ AVR_DI int pgs4(const KModel &m, const NS &ns, const CS &cs, lds_i *list, lds_i 
         const int r0 = fwd ? 0 : n_nc - 1, sg = fwd ? 1 : -1;
         const int ob = ns.eo + r0 * (RWC * 4);
         lds_f *ib = ns.ip0 + r0;
-        sweep4<DN, false>(ns, anc_max, [&](NR &R, int j) { ns.set(R, j < a_nc, ob + sg * j * (RWC * 4), ib + sg * j); },
+        // (B4_ADDR: row min(no + sg j, n_nc) as unsigned numbers, row n_nc the null row: forward
+        // no = n_nc - a_nc; backward no = a_nc - 1, which wraps past the rows for j >= a_nc)
+        const int no = fwd ? n_nc - a_nc : a_nc - 1;
+        sweep4<DN, false>(ns, anc_max, [&](NR &R, int j) {
+                              if constexpr (NS::addr) {
+                                  const unsigned k = min((unsigned)(no + sg * j), (unsigned)n_nc);
+                                  R.o = ns.eo + (int)__umul24(k, (unsigned)(RWC * 4));
+                                  R.ip = ns.ip0 + k;
+                              } else ns.set(R, j < a_nc, ob + sg * j * (RWC * 4), ib + sg * j);
+                          },
                           [&](const NR &R) { *R.ip = go4<true>(R, d, R.imp, R.h0.z, R.h0.w, R.h1.x, R.h1.y, R.h1.z, &acc); });
-        auto at_na = [&](CR &R, int j) { cs.set(R, j < a_c, cs.cn + CRW * 4 * j, cs.ipn + j); };
+        unsigned nb = cs.cn + CRW * 4 * (n_c - a_c);                                // (B4_ADDR) record / slot of index 0
+        lds_c *const nib = (lds_c *)cs.ipn + 12 * (n_c - a_c);
+        // (an opaque value: left visible, the compiler sums k + (n_c - a_c) per row before the shift-add)
+        if constexpr (CS::addr) asm("" : "+v"(nb));
+        auto at_na = [&](CR &R, int j) {
+            if constexpr (CS::addr) {
+                const unsigned k = (unsigned)min(j, a_c);
+                R.wb = nb + CRW * 4 * k;
+                R.ip = (lds_f *)(nib + __umul24(k, 12u));
+            } else cs.set(R, j < a_c, cs.cn + CRW * 4 * j, cs.ipn + j);
+        };
         sweep4<DC, false>(cs, ac_max, at_na, [&](const CR &R) { *R.ip = go4<CS::robot_parts>(R, d, R.imp, R.h.y, R.h.z, 0.f, 1e10f, R.h.w, &acc); });
         // active contacts (positive normal impulse) of each group, in contact order
         int t = 0;
         for (int c0 = 0; c0 < ac_max; c0 += 16) {
             const int c = c0 + sl;
-            const bool a = c < a_c && cs.ipn[c < a_c ? c : 0] > 0.f;
+            const bool a = c < a_c && cs.ipn[(CS::addr ? 3 : 1) * (c < a_c ? c : 0)] > 0.f;
             const unsigned long long b = __ballot(a);
             const unsigned gm = (unsigned)(b >> (lane_id() & 48)) & 0xffffu;
-            if (a) list[t + __popc(gm & ((1u << sl) - 1u))] = c;
+            if constexpr (CS::addr) {   // the unit's first record | its impulse triple << 16
+                if (a) list[t + __popc(gm & ((1u << sl) - 1u))] = (int)((cs.cf + 2 * CRW * 4 * c) | lds_addr(cs.ipf + 3 * c) << 16);
+            } else if (a) list[t + __popc(gm & ((1u << sl) - 1u))] = c;
             t += __popc(gm);
         }
+        if constexpr (CS::addr) list[t] = (int)((unsigned)LNB_NULL | lds_addr(cs.nullip) << 16);     // the null unit
         const int tmax = wave_max4(t);
         units += tmax;
         if (tmax > 0) {
@@ -4317,13 +4371,24 @@ AVR_DI int pgs4(const KModel &m, const NS &ns, const CS &cs, lds_i *list, lds_i 
         // the headers they address
         constexpr int K = 2 * DC + 1;
         Pair4<CS> X[K];
-        auto lst = [&](int u) { const int c = list[u < t ? u : 0]; return u < t ? c : -1; };   // (unconditional read)
+        auto lst = [&](int u) {     // (unconditional read; B4_ADDR: entry t is the null unit)
+            if constexpr (CS::addr) return list[min(u, t)];
+            else { const int c = list[u < t ? u : 0]; return u < t ? c : -1; }
+        };
         auto hdr = [&](Pair4<CS> &Y, int c) {
-            cs.set(Y.a, c >= 0, cs.cf + 2 * CRW * 4 * c, cs.ipf + 2 * c);
-            cs.hdr(Y.a);
-            cs.hdr2(Y.b, Y.a);
-            const float x = cs.ipn[max(c, 0)];     // (read unconditionally: no branch in the pipeline)
-            Y.in = c >= 0 ? x : 0.f;
+            if constexpr (CS::addr) {
+                Y.a.wb = (unsigned)c & 0xffffu;
+                Y.a.ip = lds_at((unsigned)c >> 16);
+                cs.hdr(Y.a);
+                cs.hdr2(Y.b, Y.a);
+                Y.in = Y.a.ip[2];                  // (the null triple's normal slot stays 0)
+            } else {
+                cs.set(Y.a, c >= 0, cs.cf + 2 * CRW * 4 * c, cs.ipf + 2 * c);
+                cs.hdr(Y.a);
+                cs.hdr2(Y.b, Y.a);
+                const float x = cs.ipn[max(c, 0)];     // (read unconditionally: no branch in the pipeline)
+                Y.in = c >= 0 ? x : 0.f;
+            }
         };
         auto go = [&](const Pair4<CS> &Y) {
             const float lim = Y.a.h.w * Y.in;
@@ -4357,7 +4422,44 @@ AVR_DI int pgs4(const KModel &m, const NS &ns, const CS &cs, lds_i *list, lds_i 
         // torsional index) pairs compacted from the active list, then one flat sweep, step j = row
         // j mod 3 of the j / 3-th such contact; a row carries its contact's normal impulse (its
         // limits are +-coefficient x that impulse)
-        {
+        if constexpr (CS::addr) {
+            // B4_ADDR: three consecutive row entries per such contact, (record | impulse slot << 16,
+            // the contact's normal impulse), so step j reads entry min(j, rows); entry rows is a
+            // null row with normal impulse 0
+            typedef __attribute__((address_space(3))) u2v lds_u2;
+            lds_u2 *const tl = (lds_u2 *)tlist;
+            int tt = 0;
+            for (int u0 = 0; u0 < tmax; u0 += 16) {
+                const int u = u0 + sl;
+                const unsigned e = (unsigned)list[min(u, t)];
+                const int c = u < t ? (int)((e & 0xffffu) - cs.cf) >> 7 : 0;    // (2 CRW 4 = 128 bytes per unit)
+                const int tv = cs.tor_of(c);                 // (read unconditionally, record 0 past the list)
+                const float in = lds_at(e >> 16)[2];
+                const bool a = u < t && tv > 0;
+                const unsigned long long b = __ballot(a);
+                const unsigned gm = (unsigned)(b >> (lane_id() & 48)) & 0xffffu;
+                if (a) {
+                    lds_u2 *const q = tl + 3 * (tt + __popc(gm & ((1u << sl) - 1u)));
+                    const unsigned w = (cs.ct + 3 * CRW * 4 * (tv - 1)) | lds_addr(cs.ipt + 3 * (tv - 1)) << 16;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) q[k] = u2v{w + k * (CRW * 4 + (4 << 16)), (unsigned)__float_as_int(in)};
+                }
+                tt += __popc(gm);
+            }
+            const int tr = 3 * tt;
+            tl[tr] = u2v{(unsigned)LNB_NULL | lds_addr(cs.nullip) << 16, 0u};
+            const int ttmax = wave_max4(tt);
+            const TorSrc<CS> ts{cs};
+            sweep4<DC, false>(ts, 3 * ttmax, [&](TorRow<CS> &R, int j) {
+                const u2v e = tl[min(j, tr)];
+                R.wb = e.x & 0xffffu;
+                R.ip = lds_at(e.x >> 16);
+                R.in = __uint_as_float(e.y);
+            }, [&](const TorRow<CS> &R) {
+                const float lim = R.h.w * R.in;
+                *R.ip = go4<CS::robot_parts>(R, d, R.imp, R.h.y, R.h.z, -lim, lim, BT_RESIDUAL_SQRT * R.h.y, &acc);
+            });
+        } else {
             int tt = 0;
             for (int u0 = 0; u0 < tmax; u0 += 16) {
                 const int u = u0 + sl;
@@ -4498,9 +4600,19 @@ AVR_DI void substep_b4_block(const KModel &m, float *__restrict__ state, const u
     SYNC();
 #endif
     // pack the groups' regions; stage every row (B4_NC_LDS) or the contact rows when all four fit
-    const int szA = al4(n_rows + 2) + (K_TORSION ? 2 : 1) * al4(n_c), szB = n_cr * CRW + n_rc * ROBW;
+#if B4_ADDR
+    // (impulses with the null triple and the null non-contact slot; the list with its null entry;
+    // two words per torsional row entry and a null one; the null headers among the records)
+    constexpr int GN = 4, GNC = 8;      // words of the null header after the normal / the non-contact records
+    const int n_imp = n_rows + 3 + B4_NP;
+    const int szA = al4(n_imp) + al4(n_c + 1) + (K_TORSION ? al4(6 * n_t + 2) : 0), szB = n_cr * CRW + n_rc * ROBW + GN;
+#else
+    constexpr int GN = 0, GNC = 0;
+    const int n_imp = n_rows + 2;
+    const int szA = al4(n_imp) + (K_TORSION ? 2 : 1) * al4(n_c), szB = n_cr * CRW + n_rc * ROBW;
+#endif
 #if B4_NC_LDS
-    const int szF = szB + n_nc * (RWC + ROBW);
+    const int szF = szB + n_nc * (RWC + ROBW) + GNC;
     const int f0 = __shfl(szA + szF, 0), f1 = __shfl(szA + szF, 16), f2 = __shfl(szA + szF, 32), f3 = __shfl(szA + szF, 48);
     const bool full = uni(f0 + f1 + f2 + f3) <= B4_LDSW - LN_HEAD && !m.b4_global;
 #else
@@ -4518,11 +4630,21 @@ AVR_DI void substep_b4_block(const KModel &m, float *__restrict__ state, const u
     }
     base += LN_HEAD;
     lds_f *imp = blk + base;
-    lds_i *list = (lds_i *)(imp + al4(n_rows + 2));
-    lds_i *tlist = list + al4(n_c);     // (K_TORSION) active contacts with torsional rows
+    lds_i *list = (lds_i *)(imp + al4(n_imp));
+    lds_i *tlist = list + al4(n_c + (B4_ADDR ? 1 : 0));     // (K_TORSION) active contacts with torsional rows
     // LDS regions: contact records at cw, then (full) the non-contact records at nw, then the
-    // robot parts at rw (full: every slot's; otherwise the robot-contact slots')
-    const int cw = base + szA, nw = cw + n_cr * CRW, rw = full ? nw + n_nc * RWC : nw;
+    // robot parts at rw (full: every slot's; otherwise the robot-contact slots'); B4_ADDR: GN null
+    // words after the normal records, GNC after the non-contact records
+    const int cw = base + szA, nw = cw + n_cr * CRW + GN, rw = full ? nw + n_nc * RWC + GNC : nw;
+    // impulse slots: B4_ADDR and rows in LDS: non-contact rows, (B4_NP) a null slot, torsional rows,
+    // a (friction, friction, normal) triple per contact, the null triple; otherwise rows 0 ..
+    // n_rows - 1 (non-contact, normal, friction pairs, torsional), then 2 null slots
+    const bool trip = B4_ADDR && in_lds;
+    const int ins = trip ? 3 : 1;       // words between two normal impulses
+    lds_f *const ipt = trip ? imp + n_nc + B4_NP : imp + n_nc + 3 * n_c;
+    lds_f *const ipf = trip ? ipt + 3 * n_t : imp + n_nc + n_c;
+    lds_f *const ipn = trip ? ipf + 2 : imp + n_nc;
+    lds_f *const nullip = trip ? ipf + 3 * n_c : imp + n_rows;
     // starting impulses: non-contact rows and frictions 0, normal rows the cached impulse x the
     // warm-start factor; null slots 0.  The cached impulses are loaded here and stored after the
     // staging loads below have been issued (one memory round trip for both).
@@ -4530,9 +4652,9 @@ AVR_DI void substep_b4_block(const KModel &m, float *__restrict__ state, const u
     float wimp[K_MAX_CONTACTS / 16];
 #pragma unroll
     for (int q = 0; q < K_MAX_CONTACTS / 16; q++) wimp[q] = cpool[AVR_CP_WORDS * min(sl + 16 * q, max(n_c - 1, 0)) + AVR_CP_IMP];
-    for (int r = sl; r < n_rows + 2; r += 16) {
-        const int c = r - n_nc;
-        if (!(c >= 0 && c < n_c)) imp[r] = 0.f;
+    for (int r = sl; r < n_imp; r += 16) {
+        const int c = r - (int)(ipn - imp);     // (a normal slot: c = ins x its contact)
+        if (!(c >= 0 && c < ins * n_c && (!trip || c % 3 == 0))) imp[r] = 0.f;
     }
     for (int i = lane; i < LN_HEAD; i += 64) blk[i] = 0.f;        // null rows, zero parts
     if (in_lds) {   // contact records, (full) non-contact records, robot parts: 8 loads in flight per lane
@@ -4550,23 +4672,29 @@ AVR_DI void substep_b4_block(const KModel &m, float *__restrict__ state, const u
 #pragma unroll
             for (int q = 0; q < 8; q++) {
                 const int i = b + 16 * q + sl;
+#if B4_ADDR     // (past the null header after the normal records; full: past the one after the non-contact records)
+                if (i < n4) l0[i + (i >= 4 * n_c ? GN / 4 : 0) + (full && i >= n4a ? GNC / 4 : 0)] = t[q];
+#else
                 if (i < n4) l0[i] = t[q];
+#endif
             }
         }
+#if B4_ADDR
+        if (sl == 0) l0[4 * n_c] = f4v{0.f, 0.f, 0.f, 0.f};
+        if (full && sl < GNC / 4) l0[n4a + GN / 4 + sl] = f4v{0.f, 0.f, 0.f, 0.f};
+#endif
     }
 #pragma unroll
     for (int q = 0; q < K_MAX_CONTACTS / 16; q++)
-        if (sl + 16 * q < n_c) imp[n_nc + sl + 16 * q] = wimp[q] * m.warmstart;
+        if (sl + 16 * q < n_c) ipn[ins * (sl + 16 * q)] = wimp[q] * m.warmstart;
     SYNC();
-    // impulse slots: rows 0 .. n_rows - 1 (non-contact, normal, friction pairs), then 2 null slots
-    lds_f *const ipn = imp + n_nc, *const ipf = ipn + n_c, *const ipt = ipf + 2 * n_c, *const nullip = imp + n_rows;
     NcSrc ns{rs, eo, ro, imp, nullip};
     DV d;
     int units, rcb = 0;
 #if B4_NC_LDS
     if (full) {
         // every row from LDS: robot part of the row with slot + 1 = s at rw + (s - 1) ROBW words
-        const unsigned cn = 4 * cw - 8, cf = cn + 4 * CRW * n_c, ct = cf + 8 * CRW * n_c, rob = 4 * (rw - ROBW) + RVB * sl;
+        const unsigned cn = 4 * cw - 8, cf = cn + 4 * CRW * n_c + 4 * GN, ct = cf + 8 * CRW * n_c, rob = 4 * (rw - ROBW) + RVB * sl;
         const NcLds nl{(lds_c *)blk, 4 * nw + 8, rob, imp, nullip};
         if (wmax(n_rc) > 0) {
             CLds<true> cs{(lds_c *)blk, cn, cf, rob, ipn, ipf, nullip, ct, ipt};
@@ -4580,7 +4708,7 @@ AVR_DI void substep_b4_block(const KModel &m, float *__restrict__ state, const u
 #endif
     if (in_lds) {
         // byte addresses: records - 8; robot part of slot s at rw + (s - n_nc) ROBW + 2 sl words
-        const unsigned cn = 4 * cw - 8, cf = cn + 4 * CRW * n_c, ct = cf + 8 * CRW * n_c, rob = 4 * (rw - (n_nc + 1) * ROBW) + RVB * sl;
+        const unsigned cn = 4 * cw - 8, cf = cn + 4 * CRW * n_c + 4 * GN, ct = cf + 8 * CRW * n_c, rob = 4 * (rw - (n_nc + 1) * ROBW) + RVB * sl;
         if (wmax(n_rc) > 0) {
             CLds<true> cs{(lds_c *)blk, cn, cf, rob, ipn, ipf, nullip, ct, ipt};
             units = pgs4<B4_DN, B4_DC>(m, ns, cs, list, tlist, n_nc, n_c, nnc_max, nc_max, d);
@@ -4596,7 +4724,7 @@ AVR_DI void substep_b4_block(const KModel &m, float *__restrict__ state, const u
     }
     (void)units; (void)rcb;
     // normal impulses back to the manifold points (warm start + normalForce)
-    for (int c = sl; c < n_c; c += 16) st[S_CP + AVR_CP_WORDS * c + AVR_CP_IMP] = imp[n_nc + c];
+    for (int c = sl; c < n_c; c += 16) st[S_CP + AVR_CP_WORDS * c + AVR_CP_IMP] = ipn[ins * c];
 #ifdef AVR_WAVETIME   // block timeline at its group-0 env: [1][env] (start, end); [2][env] (sweep lengths, LDS path, friction units)
     {
         const unsigned long long wt1 = __builtin_amdgcn_s_memrealtime();

@@ -36,6 +36,8 @@ VARIANTS = {
     'mclause': ('-mllvm', '-amdgpu-sched-strategy=max-memory-clause'), 'ilp': ('-mllvm', '-amdgpu-sched-strategy=max-ilp'),
     'itilp': ('-mllvm', '-amdgpu-sched-strategy=iterative-ilp'),
     'nonl': ('-DB4_NC_LDS=0',), 'fnl': ('-DB4_NC_LDS=1',), 'fnl12': ('-DB4_NC_LDS=1', '-DB4_LDSW=12288'), 'fnl11': ('-DB4_NC_LDS=1', '-DB4_LDSW=11264'), 'dnl2': ('-DB4_DNL=2',), 'noml': ('-DAVR_MINV_LAUNDER=0',),
+    # round 9: part B's LDS sweeps with the validity selects of the global sources
+    'addr0': ('-DB4_ADDR=0',), 'addr0wt': ('-DB4_ADDR=0', '-DAVR_WAVETIME'),
     'cr0': ('-DAVR_COOP_ROWS=0',), 'ccheck': ('-DAVR_COOP_CHECK',), 'cr2': ('-DAVR_COOP_ROWS=2',), 'cr8': ('-DAVR_COOP_ROWS=8',),
 }
 
