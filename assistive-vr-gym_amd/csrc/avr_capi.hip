@@ -509,6 +509,11 @@ int avr_create(const avr_config *cfg, const avr_model_desc *d, avr_sim **out) {
     k.pairs_flat = K_PAIRS_FLAT;
     if (const char *pf = getenv("AVR_PAIRS_FLAT"))
         if ((pf[0] == '0' || pf[0] == '1') && !pf[1]) k.pairs_flat = pf[0] == '1';
+    // the narrowphase's sphere-hull blocks take the contact pool's pairs first (K_NP_HOT: the task's default);
+    // AVR_NP_HOT=0|1 overrides (results are stored by pair index: the same bits either way)
+    k.np_hot = K_NP_HOT;
+    if (const char *nh = getenv("AVR_NP_HOT"))
+        if ((nh[0] == '0' || nh[0] == '1') && !nh[1]) k.np_hot = nh[0] == '1';
     if (E * (size_t)k.rowstride * sizeof(float) >= 0x7fff0000ull) {
         int r = fail(s, -2, "n_envs %d exceeds the row-buffer addressing limit (%d per handle)", cfg->n_envs, (int)(0x7fff0000ull / (k.rowstride * sizeof(float))));
         return r;
@@ -697,6 +702,7 @@ int32_t avr_n_envs(avr_sim *s) { return s ? s->cfg.n_envs : 0; }
 int32_t avr_env_groups(avr_sim *s) { return s ? s->ngroups : 0; }
 int32_t avr_dyn_split(const avr_sim *s) { return s ? s->km.dyn_split : 0; }
 int32_t avr_pairs_flat(const avr_sim *s) { return s ? s->km.pairs_flat : 0; }
+int32_t avr_np_hot(const avr_sim *s) { return s ? s->km.np_hot : 0; }
 
 #define CHECK_SIM(s)                         \
     if (!(s) || !(s)->d_state) return -1;    \

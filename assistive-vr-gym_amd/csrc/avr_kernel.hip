@@ -55,7 +55,7 @@ typedef const __attribute__((address_space(1))) f2v *gf2p;
 
 
 // --------------------------------------------------------------------------- LDS layout
-#define AVR_PROF_SLOTS 48   // diagnostic build: per-env cycle / event counters (tools/prof_phases.py)
+#define AVR_PROF_SLOTS 64   // diagnostic build: per-env cycle / event counters (tools/prof_phases.py)
 struct EnvLDS {
     float st[S_CP];     // state words before the contact cache; the cache lives in global memory
     float cm[MAXL][8], ax[MAXL][4], org[MAXL][4];
@@ -3674,8 +3674,33 @@ AVR_DI int np_coop(const KModel &m, float *cs, int n, EpaBuf &E, int rot, int bu
 #ifndef NP_WAVES
 #define NP_WAVES 4
 #endif
-AVR_DI void np_list(const KModel &m, const unsigned char *__restrict__ mask, int eb, int list, int n_envs, float2 *ent, float (*btfs)[MAXB * 8]) {
+// np_hot (KModel.np_hot, NP_ENVS == 1): a list-0 block starts the pairs that hold a point in the
+// env's contact pool first.  A pair that ends in a contact point iterates to convergence while a
+// far pair leaves in one or two steps, so with the long pairs at the head of the refill order the
+// block's last trips are not spent on a long pair that started late.  The pool's (sa | sb << 16)
+// keys (kernel a's okey) are loaded beside the staging loads into hkey; an entry whose e.y equals
+// one is hot; a stable partition (ballot and prefix per 64 entries) rewrites ent with the hot
+// entries first, list order kept inside each class.  Results are stored by pair index, so the
+// order changes no bit; an empty pool leaves list order.  The same start goes to the pairs that
+// took long last sub-step without ending in a contact point (near pairs inside the margin: about as
+// many as the pool's): the block leaves the keys of those that needed NP_LONG_IT iterations or more
+// in the env's collision scratch (CS_LONG, at most NP_LONG_KEYS), and the next sub-step's block reads
+// them behind the pool's keys.  A stale or cut-off list only changes the order.
+#define NP_HOT_KEYS ((K_MAX_CONTACTS + 3) / 4 * 4 + NP_LONG_KEYS)
+#define NP_LONG_IT 3
+AVR_DI void np_list(const KModel &m, const float *__restrict__ state, const unsigned char *__restrict__ mask, int eb, int list, int n_envs, float2 *ent,
+                    float (*btfs)[MAXB * 8], int *hkey) {
     const int lane = lane_id();
+#ifdef AVR_PROF
+    const bool want_hot = NP_ENVS == 1 && list == 0;       // (the step histogram splits by pool membership with the switch off too)
+#else
+    const bool want_hot = NP_ENVS == 1 && list == 0 && m.np_hot;
+#endif
+    // the pool's size, in the round trip of the list sizes
+    const int ncp = want_hot ? min(max((int)gld(state + (size_t)eb * K_STATE_WORDS + S_TASK + T_NCP), 0), K_MAX_CONTACTS) : 0;
+    const bool want_long = NP_ENVS == 1 && list == 0 && m.np_hot;
+    const int nlk = want_long ? min(max(__float_as_int(gld(env_cs(m, eb) + CS_NLONG)), 0), NP_LONG_KEYS) : 0;
+    const int nkey = ncp + nlk;
     // items per env (0 past the end or masked out), prefix over the block's envs
     int pre[NP_ENVS + 1];
     pre[0] = 0;
@@ -3712,10 +3737,60 @@ AVR_DI void np_list(const KModel &m, const unsigned char *__restrict__ mask, int
         float te[NB_OF(2 * MAXSP)], tb[NB_OF(MAXB * 8)];
         g2r(te, ck + (list ? CS_L1 : CS_L0), 2 * nk);
         g2r(tb, ck + CS_BTF, m.nb * 8);
+        if (NP_ENVS == 1 && want_hot) {       // the pool's keys (-1 past the pool: no entry's e.y)
+            const float *gcp = state + (size_t)eb * K_STATE_WORDS + S_CP;
+            float2 tk[NB_OF(NP_HOT_KEYS)];
+#pragma unroll
+            for (int q = 0; q < NB_OF(NP_HOT_KEYS); q++) tk[q] = *(const float2 *)(gcp + AVR_CP_WORDS * min(lane + 64 * q, max(ncp - 1, 0)) + AVR_CP_SA);
+            const int lk = __float_as_int(gld(ck + CS_LONG + min(lane, NP_LONG_KEYS - 1)));       // (behind the pool's keys)
+#pragma unroll
+            for (int q = 0; q < NB_OF(NP_HOT_KEYS); q++)
+                if (lane + 64 * q < NP_HOT_KEYS) hkey[lane + 64 * q] = lane + 64 * q < ncp ? ((int)tk[q].x | ((int)tk[q].y << 16)) : -1;
+            if (lane < nlk) hkey[ncp + lane] = lk;
+        }
         r2l((float *)ent + 2 * pre[k], te, 2 * nk);
         r2l(btfs[k], tb, m.nb * 8);
     }
     SYNC();
+    // hot entries and the stable partition; nh: the hot entries, at ent[0 .. nh) from here on
+    int nh = 0;
+#ifdef AVR_PROF
+    unsigned long long hm[MAXSP / 64] = {};       // hot masks in list order (the switch off: the order kept)
+#endif
+    if (NP_ENVS == 1 && want_hot && nkey > 0 && T > 0) {
+        float2 ev[MAXSP / 64];
+        bool hot[MAXSP / 64];
+#pragma unroll
+        for (int q = 0; q < MAXSP / 64; q++) { ev[q] = ent[min(lane + 64 * q, T - 1)]; hot[q] = false; }
+        for (int c = 0; 4 * c < nkey; c++) {
+            const int4 k4 = ((const int4 *)hkey)[c];
+#pragma unroll
+            for (int q = 0; q < MAXSP / 64; q++) {
+                const int y = __float_as_int(ev[q].y);
+                hot[q] = hot[q] || y == k4.x || y == k4.y || y == k4.z || y == k4.w;
+            }
+        }
+        unsigned long long bm[MAXSP / 64];
+#pragma unroll
+        for (int q = 0; q < MAXSP / 64; q++) { bm[q] = __ballot(hot[q] && lane + 64 * q < T); nh += __popcll(bm[q]); }
+#ifdef AVR_PROF
+#pragma unroll
+        for (int q = 0; q < MAXSP / 64; q++) hm[q] = bm[q];
+        if (m.np_hot)
+#endif
+        if (nh > 0 && nh < T) {
+            SYNC();                          // (every lane holds its entries: ent is rewritten)
+            int before = 0;
+#pragma unroll
+            for (int q = 0; q < MAXSP / 64; q++) {
+                const int idx = lane + 64 * q;
+                const int hp = before + __popcll(bm[q] & ((1ull << lane) - 1ull));     // hot entries ahead of idx
+                if (idx < T) ent[hot[q] ? hp : nh + idx - hp] = ev[q];
+                before += __popcll(bm[q]);
+            }
+            SYNC();
+        }
+    }
     auto entry = [&](int j) { const float2 x = ent[j]; return make_int2(__float_as_int(x.x), __float_as_int(x.y)); };
 #ifdef AVR_WAVETIME   // [3][eb] (list-0 block, list-1 block) durations in 100 MHz ticks
     struct WtNp {
@@ -3734,10 +3809,26 @@ AVR_DI void np_list(const KModel &m, const unsigned char *__restrict__ mask, int
         PH P;
         float *pcs = nullptr;      // the env of the lane's pair
         bool act = lane < T;
-        if (act) { (void)item(lane, pcs); ph_init(m, btfs[slot_of(lane)], entry(lane), P, cs_vrow(m, pcs)); }
+        int pkey = 0;              // its e.y (np_hot: the key a long pair leaves for the next sub-step)
+        if (act) { (void)item(lane, pcs); const int2 e = entry(lane); pkey = e.y; ph_init(m, btfs[slot_of(lane)], e, P, cs_vrow(m, pcs)); }
         int next = 64;
+        int nlong = 0;             // long pairs without a contact point so far
+        float *lcs = env_cs(m, eb);
 #ifdef AVR_PROF
         pcount(32, T);
+        pcount(46, nh);
+        // ph_step calls per finished pair: slots 48-55 pairs with a key in the pool (1 .. 7, 8 or
+        // more steps), 56-63 the others
+        auto is_hot = [&](int j) {
+            if (m.np_hot) return j < nh;
+            bool h = false;
+#pragma unroll
+            for (int q = 0; q < MAXSP / 64; q++)
+                if ((j >> 6) == q) h = (hm[q] >> (j & 63)) & 1ull;
+            return h;
+        };
+        int psteps = 0;
+        bool phot = is_hot(lane);
 #endif
         while (__ballot(act)) {
 #ifdef AVR_PROF
@@ -3751,15 +3842,33 @@ AVR_DI void np_list(const KModel &m, const unsigned char *__restrict__ mask, int
             if (act) {
                 done = ph_step(m, P, rc, nB, pB, d);
                 if (done) np_store(pcs, P.k, rc, nB, pB, d);
+#ifdef AVR_PROF
+                psteps++;
+                if (done && pr) atomicAdd(pr + (phot ? 48 : 56) + min(psteps, 8) - 1, 1ull);
+#endif
             }
             const unsigned long long dm = __ballot(done);
+            if (want_long) {
+                const bool lg = done && rc != 1 && P.it >= NP_LONG_IT;
+                const unsigned long long lm = __ballot(lg);
+                if (lm) {
+                    const int pos = nlong + __popcll(lm & ((1ull << lane) - 1ull));
+                    if (lg && pos < NP_LONG_KEYS) lcs[CS_LONG + pos] = __int_as_float(pkey);
+                    nlong += __popcll(lm);
+                }
+            }
             if (done) {
                 const int j = next + __popcll(dm & ((1ull << lane) - 1ull));
                 act = j < T;
-                if (act) { (void)item(j, pcs); ph_init(m, btfs[slot_of(j)], entry(j), P, cs_vrow(m, pcs)); }
+                if (act) { (void)item(j, pcs); const int2 e = entry(j); pkey = e.y; ph_init(m, btfs[slot_of(j)], e, P, cs_vrow(m, pcs)); }
+#ifdef AVR_PROF
+                psteps = 0;
+                phot = is_hot(j);
+#endif
             }
             next += __popcll(dm);
         }
+        if (want_long && lane == 0) lcs[CS_NLONG] = __int_as_float(min(nlong, NP_LONG_KEYS));
         return;
     }
 #ifdef AVR_PROF
@@ -3805,14 +3914,15 @@ AVR_DI void np_list(const KModel &m, const unsigned char *__restrict__ mask, int
     }
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NP_WAVES))) void avr_narrowphase_kernel(const KModel *__restrict__ mp, const unsigned char *__restrict__ mask, int env0,
-                                                             int n_envs) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NP_WAVES))) void avr_narrowphase_kernel(const KModel *__restrict__ mp, const float *__restrict__ state,
+                                                             const unsigned char *__restrict__ mask, int env0, int n_envs) {
     const int list = (blockIdx.x >> 3) & 1;
     const int eb = env0 + 8 * NP_ENVS * (blockIdx.x >> 4) + (blockIdx.x & 7);
     if (eb >= n_envs) return;
     __shared__ float2 ent[NP_ENVS * MAXSP];
     __shared__ float btfs[NP_ENVS][MAXB * 8];
-    np_list(*mp, mask, eb, list, n_envs, ent, btfs);
+    __shared__ __attribute__((aligned(16))) int hkey[NP_HOT_KEYS];       // np_hot: the env's contact pool keys
+    np_list(*mp, state, mask, eb, list, n_envs, ent, btfs, hkey);
 }
 
 // AVR_COOP_KERNEL 1: the wave-cooperative pairs run in a kernel of their own between the
@@ -4944,7 +5054,7 @@ hipError_t avr_launch_step(const KModel *h_m, const KModel *d_m, float *state, c
         hipLaunchKernelGGL(avr_substep_pairs_kernel, dim3(K_DYN_ROLE && h_m->dyn_split ? 16 * ((n_envs + 7) / 8) : n_envs), dim3(64), 0, stream, d_m, state,
                            mask, h, env0, env1);
         mark(AVR_K_NARROW);
-        hipLaunchKernelGGL(avr_narrowphase_kernel, dim3(16 * ((n_envs + 8 * NP_ENVS - 1) / (8 * NP_ENVS))), dim3(64), 0, stream, d_m, mask, env0, env1);
+        hipLaunchKernelGGL(avr_narrowphase_kernel, dim3(16 * ((n_envs + 8 * NP_ENVS - 1) / (8 * NP_ENVS))), dim3(64), 0, stream, d_m, state, mask, env0, env1);
 #if AVR_COOP_KERNEL
         mark(AVR_K_COOP);
         hipLaunchKernelGGL(avr_coop_kernel, dim3(n_envs), dim3(64), 0, stream, d_m, mask, env0, env1);

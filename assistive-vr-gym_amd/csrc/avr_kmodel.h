@@ -56,7 +56,11 @@ static_assert(MAXD <= 16 * NDL && MAXL <= 32, "DoF slots per lane / 32-bit link 
 #define CS_L1 (CS_L0 + 2 * MAXSP)                   // [MAXSP][2] the other pairs, ascending, the same entries
 #define CS_COOP (CS_L1 + 2 * MAXSP)                 // nonzero: some pair of this sub-step was left to the coop kernel (rc 2)
 #define CS_VROW (CS_COOP + 1)                       // int bits: the env's row of the per-variant shape / body tables (0: base)
-#define CS_WORDS (CS_COOP + 4)                      // (keeps every env's CS_RES 16-byte aligned)
+#define CS_NLONG (CS_COOP + 2)                      // int bits: entries of CS_LONG
+#define CS_LONG (CS_COOP + 4)                       // [NP_LONG_KEYS] (sa | sb << 16) of the sphere-hull pairs that took NP_LONG_IT or more GJK
+                                                    // iterations without ending in a contact point, last sub-step (np_hot: started early next time)
+#define NP_LONG_KEYS 32
+#define CS_WORDS (CS_LONG + NP_LONG_KEYS)           // (keeps every env's CS_RES 16-byte aligned)
 // Per-env dynamics hand-over (m.dynho, HO_WORDS floats per env), written by the pair launch's
 // dynamics role and read by kernel a's contact rows when m.dyn_split is set.  The unconstrained
 // velocities and the non-contact row count go through the workspace (WS_VQ, WS_FV, WS_FW, WS_NNC),
@@ -138,6 +142,8 @@ struct KModel {
                                // velocities and non-contact rows there, kernel a keeps the manifold update and contact rows
     int pairs_flat;            // the pair kernel enumerates the child shape pairs in flat passes over all active pairs
                                // (AVR_PAIRS_FLAT=0|1; per-task default K_PAIRS_FLAT), else one compound pair at a time
+    int np_hot;                // the narrowphase's sphere-hull blocks start the pairs of the env's contact pool first
+                               // (AVR_NP_HOT=0|1; per-task default K_NP_HOT), else list order
     float *dynho;              // per-env dynamics hand-over between the dynamics role and kernel a: [n_envs][HO_WORDS]
     float *ws;                 // per-env workspace between sub-step kernels: [n_envs][128]
     float *cscr;               // per-env collision scratch between the part-A kernels: [n_envs][CS_WORDS]

@@ -262,6 +262,11 @@ int32_t avr_dyn_split(const avr_sim *sim);
  * (the task's default, AVR_PAIRS_FLAT=0|1 in the environment at avr_create overrides), else 0.
  * The pair list is the same set in the same order either way.  No reference counterpart (diagnostic). */
 int32_t avr_pairs_flat(const avr_sim *sim);
+/* 1 when the narrowphase's sphere-hull blocks start the shape pairs that hold a point in the env's
+ * contact pool before the others (the task's default, AVR_NP_HOT=0|1 in the environment at avr_create
+ * overrides), else 0: list order.  Results are stored by pair index and do not depend on it.  No
+ * reference counterpart (diagnostic). */
+int32_t avr_np_hot(const avr_sim *sim);
 /* Graph captures made by this handle so far (each distinct step key captures once; a few keys
  * are cached).  No reference counterpart (diagnostic). */
 int64_t avr_graph_captures(avr_sim *sim);

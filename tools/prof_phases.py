@@ -20,14 +20,15 @@ else:
     S, _ = bench.reset_pool(TASK, A, md, list(range(min(N, 64))), os.environ.get('IMPAIRMENT', 'random'))
 S = np.tile(S, ((N + len(S) - 1) // len(S), 1))[:N]
 sim = _lib.Sim(md, N)
-SLOTS = 48
+SLOTS = 64
 prof = torch.zeros(N * SLOTS, dtype=torch.int64, device='cuda')
 lib.avr_set_profile_buffer(sim.h, prof.data_ptr())
 sim.set_state(S.astype(np.float32)); sim.settle(100 if TASK == 0 else 0)
 names = ['fk', 'bodies+broad', 'childpairs', 'narrow+mf', '#culleditems', '#xcd-mismatch', 'dyn', 'nc_rows', 'c_rows', 'solve', 'integrate', '#cooppairs', 'task', 'collide', '#shapepairs', '#bodypairs', ' lane-narrow', ' coop', ' manifold', '#coop sph-hull', '#coop hull-hull', '#coop other', '#coop bighull', '-',
          ' M entries', ' cholesky', ' M^-1 cols', ' bias (RNEA)', '#coop GJK it', '#coop cycles', '#coop max cyc', '-',
          '#np sph-hull', '#np other', '#np refill trips', '#np ph_steps', '#np GJK it', '#np GJK it max', '#np GJK pairs', '#np closed form',
-         '  mf match', '  mf add', '  mf refresh', '#pair loop trips', '#pair cull rounds', '#pair cull children', '-', '-']
+         '  mf match', '  mf add', '  mf refresh', '#pair loop trips', '#pair cull rounds', '#pair cull children', '#np pool pairs', '-'] + \
+        ['#np pool pair %d%s steps' % (k, '+' if k == 8 else '') for k in range(1, 9)] + ['#np other pair %d%s steps' % (k, '+' if k == 8 else '') for k in range(1, 9)]
 for t in range(int(os.environ.get('PROF_STEPS', '3'))):
     prof.zero_(); torch.cuda.synchronize()      # (the handle's streams are not ordered after torch's: zero before the step starts)
     t0 = time.time(); sim.step(_lib.random_actions(1001, np.arange(N), t)); el = time.time() - t0
@@ -53,6 +54,26 @@ if os.environ.get('PROF_JSON'):
     rec['serial rounds over flat rounds'] = (rec['loop trips'] + rec['cull rounds']) / rec['flat rounds']
     rec['childpairs share of the pair block'] = rec['childpairs cycles'] / (rec['fk cycles'] + rec['bodies+broad cycles'] + rec['childpairs cycles'])
     json.dump(dict(what='tools/prof_phases.py %d, AVR_PROF build, step %d, per env and sub-step' % (N, t), **rec), open(os.environ['PROF_JSON'], 'w'), indent=1)
+if os.environ.get('TAILS_JSON'):
+    # launch tails of the last step: ph_step calls per finished sphere-hull pair, by whether the pair holds
+    # a point in the env's contact pool; refill trips per list-0 block and sub-step; kernel a's contact rows,
+    # manifold update and cooperative pairs in the envs whose kernel a is in the slowest 1 %
+    import json
+    nsub = 10 if TASK == 0 else 5
+    steps = np.arange(1, 9)
+    hp, ho = p[:, 48:56].sum(0), p[:, 56:64].sum(0)
+    ka1 = p[:, 3] + p[:, 6] + p[:, 7] + p[:, 8]
+    slow = np.argsort(-ka1)[:max(1, N // 100)]
+    per = lambda k, e=slice(None): dict(mean=p[e, k].mean() / nsub, max=p[e, k].max() / nsub)
+    rec = dict(what='tools/prof_phases.py %d, AVR_PROF build, TASK %d, step %d, np_hot %d; cycles per env and sub-step' % (N, TASK, t, sim.np_hot()),
+               steps_per_pair_pool=dict(hist_1_to_8plus=hp.tolist(), pairs=hp.sum(), mean=float((hp * steps).sum() / max(hp.sum(), 1))),
+               steps_per_pair_other=dict(hist_1_to_8plus=ho.tolist(), pairs=ho.sum(), mean=float((ho * steps).sum() / max(ho.sum(), 1))),
+               list0_pairs_per_block=p[:, 32].mean() / nsub, list0_pool_pairs_per_block=p[:, 46].mean() / nsub,
+               list0_ph_steps_per_block=p[:, 35].mean() / nsub, list0_trips_per_block=per(34),
+               kernel_a_all=dict(c_rows=per(8), collide=per(13), manifold=per(18), coop_cycles=per(29), coop_max_pair_cycles=dict(max=p[:, 30].max())),
+               kernel_a_slowest_1pct=dict(envs=len(slow), c_rows=per(8, slow), collide=per(13, slow), manifold=per(18, slow), coop_cycles=per(29, slow),
+                                          coop_max_pair_cycles=dict(max=p[slow, 30].max())))
+    json.dump(rec, open(os.environ['TAILS_JSON'], 'w'), indent=1)
 St = sim.get_state()
 print('ncp mean', St[:, L.S_TASK + L.T_NCP].mean(), 'flags', np.unique(St[:, L.S_TASK + L.T_FLAGS]))
 # the envs with the slowest contact-row phase: their contact count and robot endpoints (last step)
