@@ -4025,10 +4025,19 @@ __global__ __launch_bounds__(64) AVR_KATTR void avr_substep_a_kernel(const KMode
 // select: the waits the compiler places for a row then count only that row's loads, and the
 // software pipeline's read-ahead (headers 2D rows ahead, the header-dependent parts D ahead)
 // stays in flight.
-#if B4_PK
-struct DV { float rq, rq2; f2v v1, v2, v3; };             // v1 = (vx, wx), v2 = (vy, wy), v3 = (vz, wz)
+// (AVR_WAVETIME builds: 100 MHz stamps inside a block, kept from moving by scheduling barriers --
+// after the staging barrier, after the warm start, at the end of iteration 0, before the epilogue)
+#ifdef AVR_WAVETIME
+#define WT_FIELDS unsigned long long wt_stage, wt_warm, wt_it0, wt_epi;
+#define WT_STAMP(x) do { __builtin_amdgcn_sched_barrier(0); (x) = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
-struct DV { float rq, rq2, vx, vy, vz, wx, wy, wz; };   // rq2: DoF sl + 16 (NDL 2)
+#define WT_FIELDS
+#define WT_STAMP(x) do { } while (0)
+#endif
+#if B4_PK
+struct DV { float rq, rq2; f2v v1, v2, v3; WT_FIELDS };   // v1 = (vx, wx), v2 = (vy, wy), v3 = (vz, wz)
+#else
+struct DV { float rq, rq2, vx, vy, vz, wx, wy, wz; WT_FIELDS };   // rq2: DoF sl + 16 (NDL 2)
 #endif
 
 AVR_DI int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
@@ -4092,6 +4101,21 @@ AVR_DI int al4(int x) { return (x + 3) & ~3; }
 #define B4_ADDR 1
 #endif
 #define B4_NP (B4_ADDR && B4_NC_LDS ? 1 : 0)     // null impulse slot after the non-contact rows
+// The part of a block's time that its row count does not set (-DB4_FIXED=0: as before), for the
+// LDS row sources only (the global-row path keeps its code and stays the in-tree reference):
+//   the active list reads every normal impulse of a group before its first ballot;
+//   the next iteration's non-contact sweep starts its reads during the current one (B4_FX_AHEAD).
+// None of them changes a result bit.  Per task (K_B4_FIXED): on for FeedingJaco, off for the PR2
+// tasks, which lose with it.
+#ifndef B4_FIXED
+#define B4_FIXED K_B4_FIXED
+#endif
+#ifndef B4_FX_LIST       // (one item off at a time in experiment builds: tools/build_variants.py)
+#define B4_FX_LIST B4_FIXED
+#endif
+#ifndef B4_FX_AHEAD
+#define B4_FX_AHEAD B4_FIXED
+#endif
 AVR_DI unsigned lds_addr(const __attribute__((address_space(3))) void *p) { return (unsigned)(size_t)p; }
 AVR_DI __attribute__((address_space(3))) float *lds_at(unsigned a) { return (__attribute__((address_space(3))) float *)(size_t)a; }
 
@@ -4354,15 +4378,21 @@ AVR_DI void hdr_of(const S &s, typename S::Row &R) {
     if constexpr (H3) s.hdr3(R);
     else s.hdr(R);
 }
-template <int D, bool H3, class S, class AT, class GO>
-AVR_DI void sweep4(const S &s, int n, const AT &at, const GO &go) {
-    if (n <= 0) return;
-    constexpr int K = 2 * D + 1;
-    typename S::Row R[K];
+// (in three parts, so that a sweep's first reads can be issued before the sweep before it has
+// ended: the headers of steps 0 .. 2D - 1, the parts of steps 0 .. D - 1, the rounds)
+template <int D, bool H3, class S, class AT>
+AVR_DI void sweep4_hdrs(const S &s, typename S::Row (&R)[2 * D + 1], const AT &at) {
 #pragma unroll
     for (int q = 0; q < 2 * D; q++) { at(R[q], q); hdr_of<D, H3>(s, R[q]); }
+}
+template <int D, class S>
+AVR_DI void sweep4_parts(const S &s, typename S::Row (&R)[2 * D + 1]) {
 #pragma unroll
     for (int q = 0; q < D; q++) s.parts(R[q]);
+}
+template <int D, bool H3, class S, class AT, class GO>
+AVR_DI void sweep4_rounds(const S &s, int n, typename S::Row (&R)[2 * D + 1], const AT &at, const GO &go) {
+    constexpr int K = 2 * D + 1;
     for (int j = 0; j < n; j += K) {
 #pragma unroll
         for (int q = 0; q < K; q++) {
@@ -4372,6 +4402,14 @@ AVR_DI void sweep4(const S &s, int n, const AT &at, const GO &go) {
             go(R[q]);
         }
     }
+}
+template <int D, bool H3, class S, class AT, class GO>
+AVR_DI void sweep4(const S &s, int n, const AT &at, const GO &go) {
+    if (n <= 0) return;
+    typename S::Row R[2 * D + 1];
+    sweep4_hdrs<D, H3>(s, R, at);
+    sweep4_parts<D>(s, R);
+    sweep4_rounds<D, H3>(s, n, R, at, go);
 }
 
 // friction unit: the two friction rows of one active contact and that contact's normal impulse
@@ -4424,31 +4462,54 @@ AVR_DI int pgs4(const KModel &m, const NS &ns, const CS &cs, lds_i *list, lds_i 
     // warm start (normal rows, contact order): delta = cached impulse x warm-start factor, which
     // is also the rows' starting impulse
     sweep4<DC, true>(cs, nc_max, at_n, [&](const CR &R) { (void)go4<CS::robot_parts>(R, d, 0.f, R.h.y, R.h.z, R.imp, R.imp); });
+    WT_STAMP(d.wt_warm);
+#ifdef AVR_WAVETIME
+    d.wt_it0 = d.wt_warm;
+#endif
     int units = 0;      // friction units swept (diagnostics)
     // solverResidualThreshold: a group whose rows all stayed within their residual limits in an
     // iteration is done -- its rows are null rows from then on (Bullet leaves that solve group's
     // PGS loop), and the wave leaves the loop once its four groups are done
     bool done = false;
+    // non-contact rows, the sweep direction alternating per iteration: step j of iteration it_
+    // with a of this group's rows active
+    // (B4_ADDR: row min(no + sg j, n_nc) as unsigned numbers, row n_nc the null row: forward
+    // no = n_nc - a; backward no = a - 1, which wraps past the rows for j >= a)
+    auto nc_at = [&](int it_, int a) {
+        const bool fwd = (it_ & 1) != 0;
+        const int r0 = fwd ? 0 : n_nc - 1, sg = fwd ? 1 : -1;
+        const int ob = ns.eo + r0 * (RWC * 4);
+        lds_f *const ib = ns.ip0 + r0;
+        const int no = fwd ? n_nc - a : a - 1;
+        return [=, &ns](NR &R, int j) {
+            if constexpr (NS::addr) {
+                const unsigned k = min((unsigned)(no + sg * j), (unsigned)n_nc);
+                R.o = ns.eo + (int)__umul24(k, (unsigned)(RWC * 4));
+                R.ip = ns.ip0 + k;
+            } else ns.set(R, j < a, ob + sg * j * (RWC * 4), ib + sg * j);
+        };
+    };
+    // B4_FX_AHEAD (non-contact rows from global memory beside contact rows in LDS): the first reads
+    // of iteration it + 1's non-contact sweep -- two dependent L2 round trips, headers and then
+    // the parts they address -- are issued during iteration it, the headers after its normal sweep
+    // and the parts before its friction sweep, which uses the LDS only.  The records are not written
+    // during the solve, and a non-contact row's impulse slot is written by the non-contact sweep
+    // alone, so a slot read after iteration it's normal sweep holds the value iteration it + 1
+    // starts from.  The reads assume that the group's done stays as it is; in an iteration that
+    // changes some group's done they are issued again.
+    constexpr bool AHEAD = B4_FX_AHEAD && CS::addr && !NS::addr;
+    NR Rn[2 * DN + 1];
+    if constexpr (AHEAD) {
+        sweep4_hdrs<DN, false>(ns, Rn, nc_at(0, n_nc));
+        sweep4_parts<DN>(ns, Rn);
+    }
     for (int it = 0; it < m.iters; it++) {
         const int a_nc = done ? 0 : n_nc, a_c = done ? 0 : n_c;         // this iteration's rows
         const int anc_max = wave_max4(a_nc), ac_max = wave_max4(a_c);
         unsigned long long acc = 0ull;      // lanes of groups with a row above its residual limit
-        // non-contact rows, the sweep direction alternating per iteration
-        const bool fwd = (it & 1) != 0;
-        const int r0 = fwd ? 0 : n_nc - 1, sg = fwd ? 1 : -1;
-        const int ob = ns.eo + r0 * (RWC * 4);
-        lds_f *ib = ns.ip0 + r0;
-        // (B4_ADDR: row min(no + sg j, n_nc) as unsigned numbers, row n_nc the null row: forward
-        // no = n_nc - a_nc; backward no = a_nc - 1, which wraps past the rows for j >= a_nc)
-        const int no = fwd ? n_nc - a_nc : a_nc - 1;
-        sweep4<DN, false>(ns, anc_max, [&](NR &R, int j) {
-                              if constexpr (NS::addr) {
-                                  const unsigned k = min((unsigned)(no + sg * j), (unsigned)n_nc);
-                                  R.o = ns.eo + (int)__umul24(k, (unsigned)(RWC * 4));
-                                  R.ip = ns.ip0 + k;
-                              } else ns.set(R, j < a_nc, ob + sg * j * (RWC * 4), ib + sg * j);
-                          },
-                          [&](const NR &R) { *R.ip = go4<true>(R, d, R.imp, R.h0.z, R.h0.w, R.h1.x, R.h1.y, R.h1.z, &acc); });
+        const auto go_nc = [&](const NR &R) { *R.ip = go4<true>(R, d, R.imp, R.h0.z, R.h0.w, R.h1.x, R.h1.y, R.h1.z, &acc); };
+        if constexpr (AHEAD) sweep4_rounds<DN, false>(ns, anc_max, Rn, nc_at(it, a_nc), go_nc);
+        else sweep4<DN, false>(ns, anc_max, nc_at(it, a_nc), go_nc);
         unsigned nb = cs.cn + CRW * 4 * (n_c - a_c);                                // (B4_ADDR) record / slot of index 0
         lds_c *const nib = (lds_c *)cs.ipn + 12 * (n_c - a_c);
         // (an opaque value: left visible, the compiler sums k + (n_c - a_c) per row before the shift-add)
@@ -4461,8 +4522,31 @@ AVR_DI int pgs4(const KModel &m, const NS &ns, const CS &cs, lds_i *list, lds_i 
             } else cs.set(R, j < a_c, cs.cn + CRW * 4 * j, cs.ipn + j);
         };
         sweep4<DC, false>(cs, ac_max, at_na, [&](const CR &R) { *R.ip = go4<CS::robot_parts>(R, d, R.imp, R.h.y, R.h.z, 0.f, 1e10f, R.h.w, &acc); });
+        if constexpr (AHEAD) sweep4_hdrs<DN, false>(ns, Rn, nc_at(it + 1, a_nc));
         // active contacts (positive normal impulse) of each group, in contact order
         int t = 0;
+        if constexpr (B4_FX_LIST && CS::addr) {
+            // every round's normal impulse read before the first ballot (one LDS latency, not one
+            // per 16 contacts): the normal sweep above wrote them and nothing writes them before the
+            // next iteration's normal sweep, so a read issued here sees the final value; a lane past
+            // its group's contacts reads contact 0's slot (n_c = 0: the null triple's, ipn + 0) and
+            // does not use it
+            constexpr int NR = (K_MAX_CONTACTS + 15) / 16;
+            float in[NR];
+#pragma unroll
+            for (int q = 0; q < NR; q++) { const int c = 16 * q + sl; in[q] = cs.ipn[3 * (c < a_c ? c : 0)]; }
+#pragma unroll
+            for (int q = 0; q < NR; q++) {
+                if (16 * q < ac_max) {
+                    const int c = 16 * q + sl;
+                    const bool a = c < a_c && in[q] > 0.f;
+                    const unsigned long long b = __ballot(a);
+                    const unsigned gm = (unsigned)(b >> (lane_id() & 48)) & 0xffffu;
+                    if (a) list[t + __popc(gm & ((1u << sl) - 1u))] = (int)((cs.cf + 2 * CRW * 4 * c) | lds_addr(cs.ipf + 3 * c) << 16);
+                    t += __popc(gm);
+                }
+            }
+        } else
         for (int c0 = 0; c0 < ac_max; c0 += 16) {
             const int c = c0 + sl;
             const bool a = c < a_c && cs.ipn[(CS::addr ? 3 : 1) * (c < a_c ? c : 0)] > 0.f;
@@ -4476,6 +4560,7 @@ AVR_DI int pgs4(const KModel &m, const NS &ns, const CS &cs, lds_i *list, lds_i 
         if constexpr (CS::addr) list[t] = (int)((unsigned)LNB_NULL | lds_addr(cs.nullip) << 16);     // the null unit
         const int tmax = wave_max4(t);
         units += tmax;
+        if constexpr (AHEAD) sweep4_parts<DN>(ns, Rn);
         if (tmax > 0) {
         // the same depth-DC pipeline over friction units; list entries are read one step before
         // the headers they address
@@ -4602,8 +4687,18 @@ AVR_DI int pgs4(const KModel &m, const NS &ns, const CS &cs, lds_i *list, lds_i 
         }
 #endif
         }   // (tmax > 0)
+        const bool was = done;
         done = done || ((acc >> (lane_id() & 48)) & 0xffffull) == 0ull;
+#ifdef AVR_WAVETIME
+        if (it == 0) WT_STAMP(d.wt_it0);
+#endif
         if (__ballot(!done) == 0ull) break;
+        if constexpr (AHEAD) {
+            if (__ballot(done != was) != 0ull) {
+                sweep4_hdrs<DN, false>(ns, Rn, nc_at(it + 1, done ? 0 : n_nc));
+                sweep4_parts<DN>(ns, Rn);
+            }
+        }
     }
     return units;
 }
@@ -4800,6 +4895,7 @@ AVR_DI void substep_b4_block(const KModel &m, float *__restrict__ state, const u
     SYNC();
     NcSrc ns{rs, eo, ro, imp, nullip};
     DV d;
+    WT_STAMP(d.wt_stage);
     int units, rcb = 0;
 #if B4_NC_LDS
     if (full) {
@@ -4833,6 +4929,7 @@ AVR_DI void substep_b4_block(const KModel &m, float *__restrict__ state, const u
         units = pgs4<B4_DN, B4_DG>(m, ns, cs, list, tlist, n_nc, n_c, nnc_max, nc_max, d);
     }
     (void)units; (void)rcb;
+    WT_STAMP(d.wt_epi);
     // normal impulses back to the manifold points (warm start + normalForce)
     for (int c = sl; c < n_c; c += 16) st[S_CP + AVR_CP_WORDS * c + AVR_CP_IMP] = ipn[ins * c];
 #ifdef AVR_WAVETIME   // block timeline at its group-0 env: [1][env] (start, end); [2][env] (sweep lengths, LDS path, friction units)
@@ -4844,6 +4941,12 @@ AVR_DI void substep_b4_block(const KModel &m, float *__restrict__ state, const u
             m.prof[((size_t)1 * n_envs + e0) * 2 + 1] = wt1;
             m.prof[((size_t)2 * n_envs + e0) * 2] = (unsigned long long)nnc_max | (unsigned long long)nc_max << 16 | (unsigned long long)in_lds << 32;
             m.prof[((size_t)2 * n_envs + e0) * 2 + 1] = (unsigned long long)wmax(n_rows) | (unsigned long long)units << 16 | (unsigned long long)rcb << 40 | (unsigned long long)xcc_id() << 44;
+            if (e0 + 16 < n_envs) {     // the stamps inside the block, in the unused records of its group-1 and group-2 envs
+                m.prof[((size_t)1 * n_envs + e0 + 8) * 2] = d.wt_stage;
+                m.prof[((size_t)1 * n_envs + e0 + 8) * 2 + 1] = d.wt_warm;
+                m.prof[((size_t)1 * n_envs + e0 + 16) * 2] = d.wt_it0;
+                m.prof[((size_t)1 * n_envs + e0 + 16) * 2 + 1] = d.wt_epi;
+            }
         }
     }
 #endif

@@ -38,6 +38,11 @@ VARIANTS = {
     'nonl': ('-DB4_NC_LDS=0',), 'fnl': ('-DB4_NC_LDS=1',), 'fnl12': ('-DB4_NC_LDS=1', '-DB4_LDSW=12288'), 'fnl11': ('-DB4_NC_LDS=1', '-DB4_LDSW=11264'), 'dnl2': ('-DB4_DNL=2',), 'noml': ('-DAVR_MINV_LAUNDER=0',),
     # round 9: part B's LDS sweeps with the validity selects of the global sources
     'addr0': ('-DB4_ADDR=0',), 'addr0wt': ('-DB4_ADDR=0', '-DAVR_WAVETIME'),
+    # round 11: part B's fixed costs (fixed0: the parent's part B on every task; fixed1: the trims on the
+    # PR2 tasks too), one item off at a time
+    'fixed0': ('-DB4_FIXED=0',), 'fixed0wt': ('-DB4_FIXED=0', '-DAVR_WAVETIME'), 'fixed1': ('-DB4_FIXED=1',),
+    'fxlist0': ('-DB4_FIXED=1', '-DB4_FX_LIST=0'), 'fxahead0': ('-DB4_FIXED=1', '-DB4_FX_AHEAD=0'),
+    'dn3r11': ('-DB4_DN=3',),
     'cr0': ('-DAVR_COOP_ROWS=0',), 'ccheck': ('-DAVR_COOP_CHECK',), 'cr2': ('-DAVR_COOP_ROWS=2',), 'cr8': ('-DAVR_COOP_ROWS=8',),
 }
 
