@@ -24,7 +24,11 @@ EXPORTS = [
     'avr_policy_set', 'avr_policy_act_device', 'avr_rollout_policy_device',
     'avr_reset_pool_set', 'avr_rollover_enable', 'avr_rollover_device', 'avr_rollover_buffers', 'avr_rollover_set_episodes',
     'avr_human_variants_set', 'avr_human_variants', 'avr_human_variant_info', 'avr_narrowphase_query_slots',
+    'avr_gae_device', 'avr_ppo_reset', 'avr_ppo_grad_device', 'avr_ppo_adam_device', 'avr_ppo_update_device', 'avr_ppo_buffers',
+    'avr_ppo_words', 'avr_policy_block', 'avr_policy_get', 'avr_policy_obs_norm_device',
 ]
+PPO_STAT_WORDS, PPO_STATS_ROWS = 8, 256      # include/avr.h AVR_PPO_STAT_WORDS, AVR_PPO_STATS_ROWS
+PPO_STATS = ('policy_loss', 'value_loss', 'entropy', 'approx_kl', 'clip_frac', 'grad_norm')   # a statistics row's first words
 MAX_HUMAN_VARIANTS = 64      # include/avr.h AVR_MAX_HUMAN_VARIANTS
 FLAGS_FAULT_MASK = 0x1f      # include/avr.h AVR_FLAGS_FAULT_MASK: bits 0-4; bit 5 (EPA budget) is informational
 
@@ -42,6 +46,25 @@ class avr_policy_desc(C.Structure):
     ARRAYS = ('ob_mean', 'ob_var', 'a_w1', 'a_b1', 'a_w2', 'a_b2', 'mu_w', 'mu_b', 'logstd', 'c_w1', 'c_b1', 'c_w2', 'c_b2', 'c_w3', 'c_b3')
     _fields_ = [('obs_dim', C.c_int32), ('act_dim', C.c_int32), ('hidden', C.c_int32), ('n_layers', C.c_int32),
                 ('clip_obs', C.c_float), ('eps', C.c_float)] + [(k, C.c_void_p) for k in ARRAYS]
+
+
+class avr_ppo_batch(C.Structure):
+    """include/avr.h avr_ppo_batch: device pointers of a flattened [n][E] batch."""
+    ARRAYS = ('obs', 'act', 'logp', 'value', 'adv', 'ret')
+    _fields_ = [('n', C.c_int32), ('E', C.c_int32)] + [(k, C.c_void_p) for k in ARRAYS]
+
+
+class avr_ppo_params(C.Structure):
+    """include/avr.h avr_ppo_params."""
+    FLOATS = ('clip', 'vf_coef', 'ent_coef', 'max_grad_norm', 'lr', 'beta1', 'beta2', 'eps')
+    _fields_ = [(k, C.c_float) for k in FLOATS] + [('norm_adv', C.c_int32), ('clip_value', C.c_int32)]
+
+
+class avr_policy_out(C.Structure):
+    """include/avr.h avr_policy_out: host float32 arrays avr_policy_get fills, matrices [out][in]."""
+    ARRAYS = avr_policy_desc.ARRAYS
+    _fields_ = [('hidden', C.c_int32), ('has_ob_rms', C.c_int32), ('has_critic', C.c_int32), ('clip_obs', C.c_float), ('eps', C.c_float)] + [
+        (k, C.c_void_p) for k in ARRAYS]
 
 
 class avr_human_variant(C.Structure):
@@ -97,6 +120,18 @@ def load(path=LIB_PATH):
         lib.avr_human_variants.restype = C.c_int32
         lib.avr_human_variant_info.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
         lib.avr_narrowphase_query_slots.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_float, vp]
+    if hasattr(lib, 'avr_ppo_reset'):               # (absent in experiment builds of older trees)
+        lib.avr_gae_device.argtypes = [vp, C.c_int32, C.c_float, C.c_float, C.c_int32, vp, vp, vp, vp, vp]
+        lib.avr_ppo_reset.argtypes = [vp]
+        lib.avr_ppo_grad_device.argtypes = [vp, C.POINTER(avr_ppo_batch), C.POINTER(avr_ppo_params), C.c_int32, C.c_int32, vp]
+        lib.avr_ppo_adam_device.argtypes = [vp, C.POINTER(avr_ppo_params)]
+        lib.avr_ppo_update_device.argtypes = [vp, C.POINTER(avr_ppo_batch), C.POINTER(avr_ppo_params), C.c_int32, C.c_int32, vp]
+        lib.avr_ppo_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        lib.avr_ppo_words.restype = C.c_int32
+        lib.avr_policy_block.argtypes = [vp]
+        lib.avr_policy_block.restype = vp
+        lib.avr_policy_get.argtypes = [vp, C.POINTER(avr_policy_out)]
+        lib.avr_policy_obs_norm_device.argtypes = [vp, vp, vp]
     lib.avr_sync.argtypes = [vp]
     lib.avr_stream.argtypes = [vp]
     lib.avr_stream.restype = vp
@@ -381,6 +416,78 @@ class Sim:
     def rollover_set_episodes(self, episodes):
         ep = np.ascontiguousarray(episodes, np.int32).reshape(self.n)
         self._chk(self.lib.avr_rollover_set_episodes(self.h, ep.ctypes.data))
+
+    # ---- the PPO update on the device (include/avr.h avr_gae_device, avr_ppo_*)
+    def gae_device(self, n, gamma, lam, bootstrap, d_rew, d_done, d_value, d_adv, d_ret):
+        """Advantages and returns of a rollout's stacked [n, n_envs] device arrays (d_value [n+1, n_envs]);
+        bootstrap: a done bootstraps from the handle's terminal-value row instead of cutting the return."""
+        self._chk(self.lib.avr_gae_device(self.h, int(n), float(gamma), float(lam), int(bool(bootstrap)), d_rew, d_done, d_value, d_adv, d_ret))
+
+    def ppo_reset(self):
+        """Allocate / zero the optimiser state (Adam's moments, step count, gradient, statistics)."""
+        self._chk(self.lib.avr_ppo_reset(self.h))
+
+    @staticmethod
+    def ppo_batch(n, E, **ptrs):
+        """avr_ppo_batch of device pointers obs, act, logp, value, adv, ret (None: absent)."""
+        b = avr_ppo_batch(n=int(n), E=int(E))
+        for k in avr_ppo_batch.ARRAYS:
+            setattr(b, k, ptrs.get(k))
+        return b
+
+    @staticmethod
+    def ppo_params(p):
+        """avr_ppo_params from a dict with its field names (avr/ppo.py DEFAULTS has them all)."""
+        q = avr_ppo_params(norm_adv=int(bool(p['norm_adv'])), clip_value=int(bool(p['clip_value'])))
+        for k in avr_ppo_params.FLOATS:
+            setattr(q, k, float(p[k]))
+        return q
+
+    def ppo_grad_device(self, batch, params, minibatch, n_minibatch, d_perm=None):
+        """Gradient of one minibatch into the handle's gradient block (batch: ppo_batch, params: ppo_params)."""
+        self._chk(self.lib.avr_ppo_grad_device(self.h, C.byref(batch), C.byref(params), int(minibatch), int(n_minibatch), d_perm))
+
+    def ppo_adam_device(self, params):
+        """Clip the gradient block's norm and take one Adam step on the weight block in place."""
+        self._chk(self.lib.avr_ppo_adam_device(self.h, C.byref(params)))
+
+    def ppo_update_device(self, batch, params, epochs, n_minibatch, d_perm=None):
+        """epochs x n_minibatch {gradient; Adam} with no host synchronisation (d_perm: int32 [epochs, N])."""
+        self._chk(self.lib.avr_ppo_update_device(self.h, C.byref(batch), C.byref(params), int(epochs), int(n_minibatch), d_perm))
+
+    def ppo_buffers(self):
+        """Device pointers (grad, m, v: ppo_words() float32 each; stats [PPO_STATS_ROWS, PPO_STAT_WORDS])."""
+        p = [C.c_void_p() for _ in range(4)]
+        self._chk(self.lib.avr_ppo_buffers(self.h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def ppo_words(self):
+        return int(self.lib.avr_ppo_words())
+
+    def policy_block(self):
+        """Device pointer of the weight block (ppo_words() float32; None before policy_set)."""
+        return self.lib.avr_policy_block(self.h)
+
+    def policy_get(self):
+        """The installed policy's weights read back from the device: policy_set's dict (float32 arrays in
+        torch.nn.Linear's orientation; the critic's / ob_rms's entries None when absent)."""
+        o = avr_policy_out()
+        self._chk(self.lib.avr_policy_get(self.h, C.byref(o)))         # (all pointers NULL: the dimensions)
+        h, od, ad = int(o.hidden), self.obs_dim, self.act_dim
+        shapes = dict(ob_mean=(od,), ob_var=(od,), a_w1=(h, od), a_b1=(h,), a_w2=(h, h), a_b2=(h,), mu_w=(ad, h), mu_b=(ad,), logstd=(ad,),
+                      c_w1=(h, od), c_b1=(h,), c_w2=(h, h), c_b2=(h,), c_w3=(1, h), c_b3=(1,))
+        d = dict(obs_dim=od, act_dim=ad, hidden=h, n_layers=2, clip_obs=float(o.clip_obs), eps=float(o.eps))
+        for k in avr_policy_out.ARRAYS:
+            absent = (k.startswith('c_') and not o.has_critic) or (k.startswith('ob_') and not o.has_ob_rms)
+            d[k] = None if absent else np.zeros(shapes[k], np.float32)
+            if d[k] is not None:
+                setattr(o, k, d[k].ctypes.data)
+        self._chk(self.lib.avr_policy_get(self.h, C.byref(o)))
+        return d
+
+    def policy_obs_norm_device(self, d_mean, d_var):
+        """Rewrite the weight block's ob_rms rows from device float32 arrays [obs_dim] in stream order."""
+        self._chk(self.lib.avr_policy_obs_norm_device(self.h, d_mean, d_var))
 
     # ---- human height variants (include/avr.h avr_human_variants_set)
     def human_variants_set(self, records):

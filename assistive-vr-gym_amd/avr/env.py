@@ -733,6 +733,56 @@ class AVRTorchVecEnv(AVRVecEnv):
                 out['reset'] = m
         return out
 
+    # ------------------------------------------------------------------ the PPO update on the device (avr/ppo.py)
+    def compute_gae(self, out, gamma=0.99, lam=0.95, bootstrap=True):
+        """Advantages and returns [n, E] of a rollout_policy result, on the device in stream order
+        (include/avr.h avr_gae_device).  bootstrap: a done (always the TimeLimit here) bootstraps from
+        V(terminal observation) -- needs a reset pool and n <= max_episode_steps; otherwise the return
+        is cut at a done.  The tensors are the env's own, one pair per rollout length."""
+        torch = self.torch
+        n, E = out['rew'].shape
+        B = self._roll.setdefault(('gae', n), {})
+        if not B:
+            B['adv'], B['ret'] = torch.zeros(n, E, device=self.dev), torch.zeros(n, E, device=self.dev)
+        self.ext.wait_stream(torch.cuda.current_stream(self.dev))
+        self.sim.gae_device(n, gamma, lam, bootstrap, out['rew'].data_ptr(), out['done'].data_ptr(), out['value'].data_ptr(),
+                            B['adv'].data_ptr(), B['ret'].data_ptr())
+        torch.cuda.current_stream(self.dev).wait_stream(self.ext)
+        return B['adv'], B['ret']
+
+    def ppo_reset(self):
+        """Zero the optimiser state of ppo_update (Adam's moments and step count; include/avr.h
+        avr_ppo_reset).  set_policy does not do it: call this after installing a different network,
+        whose weights the old moments do not belong to."""
+        from . import _lib
+        self.sim.ppo_reset()
+        if getattr(self, '_ppo_stats', None) is None:
+            self._ppo_stats = self._wrap(self.sim.ppo_buffers()[3], (_lib.PPO_STATS_ROWS, _lib.PPO_STAT_WORDS), '<f4')
+
+    def ppo_update(self, out, adv, ret, params, epochs, n_minibatch, generator=None):
+        """epochs x n_minibatch PPO minibatch steps on the installed policy's weight block, in place and
+        in stream order (include/avr.h avr_ppo_update_device); the next rollout_policy(None, None, n)
+        runs the new weights.  out: a rollout_policy result, adv / ret: compute_gae's, params: a dict
+        with avr/ppo.py DEFAULTS' loss and Adam keys.  The minibatch permutations are torch.randperm
+        draws on the device (generator: a torch.Generator on it).  The optimiser state is zeroed by
+        ppo_reset() -- run for the caller before the env's first update only; set_policy keeps it, so
+        call ppo_reset() after installing a different network.  Returns the statistics rows [epochs * n_minibatch, 6]
+        (columns _lib.PPO_STATS), a device tensor; at most PPO_STATS_ROWS rows are kept."""
+        from . import _lib
+        torch = self.torch
+        n, E = out['rew'].shape
+        N = n * E
+        if getattr(self, '_ppo_stats', None) is None:
+            self.ppo_reset()
+        perm = torch.stack([torch.randperm(N, device=self.dev, generator=generator) for _ in range(int(epochs))]).to(torch.int32).contiguous()
+        batch = self.sim.ppo_batch(n, E, obs=out['obs'].data_ptr(), act=out['act'].data_ptr(), logp=out['logp'].data_ptr(),
+                                   value=out['value'].data_ptr(), adv=adv.data_ptr(), ret=ret.data_ptr())
+        self.ext.wait_stream(torch.cuda.current_stream(self.dev))
+        self.sim.ppo_update_device(batch, self.sim.ppo_params(params), epochs, n_minibatch, perm.data_ptr())
+        torch.cuda.current_stream(self.dev).wait_stream(self.ext)
+        rows = min(int(epochs) * int(n_minibatch), _lib.PPO_STATS_ROWS)
+        return self._ppo_stats[:rows, :len(_lib.PPO_STATS)].clone()
+
     def close(self):
         self.torch.cuda.synchronize(self.dev)
         super().close()

@@ -1,0 +1,258 @@
+"""PPO on the batched backend: the readable references of the device update (csrc/avr_ppo.hip,
+include/avr.h avr_gae_device / avr_ppo_*) and a small trainer around AVRTorchVecEnv.
+
+The loss is a2c_ppo_acktr's PPO.update (clipped surrogate, clipped value loss, entropy bonus) on the
+harness's ActorCritic (avr/policy_eval.py); the reference ships neither that library nor its
+trainer or settings, so the hyper-parameter defaults below are this facade's own choice, not the
+reference's.  gae_reference and ppo_loss_reference are the same formulas as the kernels in numpy
+and torch at any dtype: the tests use them as the reference, and they can be read next to the
+kernels.
+"""
+import numpy as np
+import torch
+
+from . import policy_eval as PE
+
+LOG_SQRT_2PI = 0.5 * float(np.log(2 * np.pi))
+
+# This facade's defaults (its own choice; see the module docstring).
+DEFAULTS = dict(
+    gamma=0.99, lam=0.95, bootstrap=True,           # advantage estimation; bootstrap: a TimeLimit done is a truncation
+    clip=0.2, vf_coef=0.5, ent_coef=0.0,            # L = L_pi + vf_coef L_v - ent_coef H
+    max_grad_norm=0.5,                              # global L2 clip
+    lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-5,      # Adam
+    norm_adv=True, clip_value=True,
+    epochs=4, n_minibatch=8,                        # passes over the batch, minibatches per pass
+    update_ob_rms=True,                             # keep VecNormalize's running observation statistics
+)
+
+# the device weight block (csrc/avr_policy.hip PW_* / PN_*), in floats
+POL_H = 64
+PW_HDR, PW_MEAN, PW_SD, PW_LOGSTD, PW_BH, PW_WH = 0, 8, 40, 72, 80, 88
+PW_NET = PW_WH + POL_H * 8
+PN_W1, PN_B1 = 0, 32 * POL_H
+PN_W2 = PN_B1 + POL_H
+PN_B2 = PN_W2 + POL_H * POL_H
+PN_WORDS = PN_B2 + POL_H
+PW_WORDS = PW_NET + 2 * PN_WORDS
+
+
+def block_live_mask(obs_dim, act_dim, hidden, has_critic=True):
+    """bool [PW_WORDS]: the words of the device weight block that hold a trainable parameter of a
+    policy of these dimensions; every other word from PW_LOGSTD on is zero padding (hidden units
+    beyond `hidden`, observation rows beyond obs_dim, head column 7 without a critic)."""
+    m = np.zeros(PW_WORDS, bool)
+    m[PW_LOGSTD:PW_LOGSTD + act_dim] = True
+    m[PW_BH:PW_BH + act_dim] = True
+    wh = np.zeros((POL_H, 8), bool)
+    wh[:hidden, :act_dim] = True
+    if has_critic:
+        m[PW_BH + 7] = True
+        wh[:hidden, 7] = True
+    m[PW_WH:PW_NET] = wh.reshape(-1)
+    for net in range(2 if has_critic else 1):
+        o = PW_NET + net * PN_WORDS
+        w1 = np.zeros((32, POL_H), bool)
+        w1[:obs_dim, :hidden] = True
+        w2 = np.zeros((POL_H, POL_H), bool)
+        w2[:hidden, :hidden] = True
+        m[o + PN_W1:o + PN_B1] = w1.reshape(-1)
+        m[o + PN_W2:o + PN_B2] = w2.reshape(-1)
+        m[o + PN_B1:o + PN_B1 + hidden] = True
+        m[o + PN_B2:o + PN_B2 + hidden] = True
+    return m
+
+
+def unpack_block(w, obs_dim, act_dim, hidden, has_critic=True):
+    """The named arrays (policy_desc's keys, [out][in]) of a host copy of a block-layout array: the
+    weight block itself, or a gradient / moment block."""
+    w = np.asarray(w)
+    d = dict(logstd=w[PW_LOGSTD:PW_LOGSTD + act_dim].copy(), mu_b=w[PW_BH:PW_BH + act_dim].copy())
+    wh = w[PW_WH:PW_NET].reshape(POL_H, 8)
+    d['mu_w'] = wh[:hidden, :act_dim].T.copy()
+    if has_critic:
+        d['c_b3'] = w[PW_BH + 7:PW_BH + 8].copy()
+        d['c_w3'] = wh[:hidden, 7][None, :].copy()
+    for net, p in enumerate('ac' if has_critic else 'a'):
+        o = PW_NET + net * PN_WORDS
+        d[p + '_w1'] = w[o + PN_W1:o + PN_B1].reshape(32, POL_H)[:obs_dim, :hidden].T.copy()
+        d[p + '_b1'] = w[o + PN_B1:o + PN_B1 + hidden].copy()
+        d[p + '_w2'] = w[o + PN_W2:o + PN_B2].reshape(POL_H, POL_H)[:hidden, :hidden].T.copy()
+        d[p + '_b2'] = w[o + PN_B2:o + PN_B2 + hidden].copy()
+    return d
+
+
+def module_params(actor_critic):
+    """{policy_desc key: the module's parameter tensor} of an ActorCritic."""
+    a, c = list(actor_critic.actor), list(actor_critic.critic)
+    return dict(a_w1=a[0].weight, a_b1=a[0].bias, a_w2=a[2].weight, a_b2=a[2].bias, mu_w=actor_critic.mu.weight, mu_b=actor_critic.mu.bias,
+                logstd=actor_critic.logstd, c_w1=c[0].weight, c_b1=c[0].bias, c_w2=c[2].weight, c_b2=c[2].bias, c_w3=c[4].weight, c_b3=c[4].bias)
+
+
+def gae_reference(rew, done, value, term_value=None, gamma=0.99, lam=0.95, bootstrap=False, dtype=np.float32):
+    """Generalised advantage estimation over stacked [n, E] arrays (value [n+1, E]) -> (adv, ret), in
+    `dtype` with the device kernel's operations in the kernel's order (float32: bit for bit):
+        nv    = done[k] ? (bootstrap ? term_value : 0) : value[k+1]
+        delta = (rew[k] + gamma * nv) - value[k]
+        gae   = delta + (gamma * lam) * (done[k] ? 0 : gae);  adv[k] = gae;  ret[k] = gae + value[k]
+    Every done of this code base is the TimeLimit: bootstrap treats it as a truncation and uses
+    V(terminal observation) (term_value [E], each env's most recent), otherwise the return is cut."""
+    T = np.dtype(dtype).type
+    rew, value = np.asarray(rew, dtype), np.asarray(value, dtype)
+    done = np.asarray(done).astype(bool)
+    n, E = rew.shape
+    assert value.shape == (n + 1, E) and done.shape == (n, E)
+    tv = np.asarray(term_value, dtype) if bootstrap else np.zeros(E, dtype)
+    g, gl = T(gamma), T(T(gamma) * T(lam))
+    adv, ret = np.zeros((n, E), dtype), np.zeros((n, E), dtype)
+    gae = np.zeros(E, dtype)
+    for k in range(n - 1, -1, -1):
+        nv = np.where(done[k], tv, value[k + 1])
+        delta = (rew[k] + g * nv) - value[k]
+        gae = delta + gl * np.where(done[k], T(0), gae)
+        adv[k] = gae
+        ret[k] = gae + value[k]
+    return adv, ret
+
+
+def ppo_loss_reference(actor_critic, ob_rms, batch, idx, params):
+    """The loss of one minibatch and its statistics, in the dtype of the module's parameters.
+
+    batch: dict of flattened tensors obs [N, obs_dim] (raw), act [N, act_dim], logp [N], value [N],
+    adv [N], ret [N]; idx: the minibatch's sample indices (LongTensor, or None: all); params: clip,
+    vf_coef, ent_coef, norm_adv, clip_value (DEFAULTS' names).  ob_rms None: no normalisation;
+    otherwise an object with mean / var (arrays or tensors) applied as policy_eval.normalize does.
+    Returns (loss, dict(policy_loss, value_loss, entropy, approx_kl, clip_frac)):
+        logp_new = sum_a -(act_a - mean_a)^2 / (2 exp(2 logstd_a)) - logstd_a - log(2 pi) / 2
+        ratio = exp(logp_new - logp);  L_pi = -mean(min(ratio A, clamp(ratio, 1 - c, 1 + c) A))
+        v_clip = value + clamp(v - value, -c, c);  L_v = 0.5 mean(max((v - ret)^2, (v_clip - ret)^2))
+        H = sum_a (0.5 + log(2 pi) / 2 + logstd_a);  L = L_pi + vf_coef L_v - ent_coef H
+    with A = (adv - mean(adv)) / (std(adv) + 1e-5) over the whole batch (unbiased std) when norm_adv."""
+    p0 = actor_critic.logstd
+    dt, dev = p0.dtype, p0.device
+    t = lambda x: torch.as_tensor(x).to(device=dev, dtype=dt)
+    adv_all = t(batch['adv'])
+    if params.get('norm_adv', True):
+        adv_all = (adv_all - adv_all.mean()) / (adv_all.std() + 1e-5)
+    sel = (lambda x: x) if idx is None else (lambda x: x[idx])
+    obs, act, logp_old, adv = sel(t(batch['obs'])), sel(t(batch['act'])), sel(t(batch['logp'])), sel(adv_all)
+    if ob_rms is not None:
+        obs = torch.clamp((obs - t(ob_rms.mean)) / torch.sqrt(t(ob_rms.var) + PE.EPS), -PE.CLIP_OBS, PE.CLIP_OBS)
+    c = float(params['clip'])
+    mean = actor_critic.mu(actor_critic.actor(obs))
+    logstd = actor_critic.logstd
+    logp = (-((act - mean) ** 2) / (2 * torch.exp(2 * logstd)) - logstd - LOG_SQRT_2PI).sum(-1)
+    ratio = torch.exp(logp - logp_old)
+    policy_loss = -torch.min(ratio * adv, torch.clamp(ratio, 1 - c, 1 + c) * adv).mean()
+    entropy = (0.5 + LOG_SQRT_2PI + logstd).sum()
+    vf = float(params.get('vf_coef', 0.0))
+    if vf != 0.0 or 'ret' in batch and batch['ret'] is not None:
+        v = actor_critic.critic(obs)[:, 0]
+        ret = sel(t(batch['ret']))
+        if params.get('clip_value', True):
+            v_old = sel(t(batch['value']))
+            v_clip = v_old + torch.clamp(v - v_old, -c, c)
+            value_loss = 0.5 * torch.max((v - ret) ** 2, (v_clip - ret) ** 2).mean()
+        else:
+            value_loss = 0.5 * ((v - ret) ** 2).mean()
+    else:
+        value_loss = torch.zeros((), dtype=dt, device=dev)
+    loss = policy_loss + vf * value_loss - float(params.get('ent_coef', 0.0)) * entropy
+    with torch.no_grad():
+        stats = dict(policy_loss=policy_loss.detach(), value_loss=value_loss.detach(), entropy=entropy.detach(),
+                     approx_kl=(logp_old - logp).mean(), clip_frac=((ratio - 1).abs() > c).to(dt).mean())
+    return loss, stats
+
+
+def flatten_rollout(out, adv, ret):
+    """rollout_policy's stacked tensors as ppo_loss_reference's flattened batch (views, no copy)."""
+    n, E = out['rew'].shape
+    N = n * E
+    return dict(obs=out['obs'][:n].reshape(N, -1), act=out['act'].reshape(N, -1), logp=out['logp'].reshape(N), value=out['value'][:n].reshape(N),
+                adv=adv.reshape(N), ret=ret.reshape(N))
+
+
+class PPOTrainer:
+    """PPO with every part of the iteration on the device: the rollout (the policy inside the rollout
+    graphs), the running observation statistics, advantage estimation and the update all run in
+    stream order with no host synchronisation; the weights live in the handle's weight block.
+
+    env: an AVRTorchVecEnv made with reset_pool=m (the device rollover keeps the episode
+    boundaries inside the rollouts); actor_critic / ob_rms: the initial policy (ob_rms None: a
+    fresh RunningMeanStd); n_steps: steps per rollout.  hyper: any of DEFAULTS' keys --
+      gamma 0.99, lam 0.95, bootstrap True (a TimeLimit done bootstraps from V(terminal observation)),
+      clip 0.2, vf_coef 0.5, ent_coef 0.0, max_grad_norm 0.5, lr 3e-4, beta1 0.9, beta2 0.999, eps 1e-5,
+      norm_adv True, clip_value True, epochs 4, n_minibatch 8, update_ob_rms True.
+    These defaults are this facade's own choice: the reference ships neither its trainer nor its
+    settings.  generator: a torch.Generator on the env's device for the minibatch permutations."""
+
+    def __init__(self, env, actor_critic, ob_rms=None, n_steps=128, generator=None, **hyper):
+        bad = set(hyper) - set(DEFAULTS)
+        if bad:
+            raise TypeError('PPOTrainer: unknown hyper-parameters %s' % sorted(bad))
+        self.hyper = dict(DEFAULTS, **hyper)
+        self.env, self.actor_critic, self.n_steps, self.generator = env, actor_critic, int(n_steps), generator
+        if env._cur is None:
+            env.reset()
+        if self.hyper['bootstrap'] and env._pool is None:
+            raise ValueError('PPOTrainer: bootstrap=True needs an env made with reset_pool=m')
+        self.ob_rms = ob_rms if ob_rms is not None else PE.RunningMeanStd((env.L.OBS_DIM,))
+        env.set_policy(actor_critic, self.ob_rms)
+        env.ppo_reset()                             # (a new network: Adam starts from zero moments)
+        dev = env.dev
+        # VecNormalize's running statistics on the device (float64; the block receives float32 copies)
+        self._mean = torch.as_tensor(np.asarray(self.ob_rms.mean, np.float64), device=dev)
+        self._var = torch.as_tensor(np.asarray(self.ob_rms.var, np.float64), device=dev)
+        self._count = torch.tensor(float(self.ob_rms.count), dtype=torch.float64, device=dev)
+        self._m32 = torch.zeros(env.L.OBS_DIM, device=dev)
+        self._v32 = torch.zeros(env.L.OBS_DIM, device=dev)
+        self.iterations = 0
+
+    def _update_ob_rms(self, obs):
+        """RunningMeanStd.update with the batch's mean / variance, on the device, then the block's rows."""
+        env, torch_ = self.env, torch
+        x = obs.reshape(-1, obs.shape[-1]).double()
+        bm, bv, bc = x.mean(0), x.var(0, unbiased=False), float(x.shape[0])
+        d = bm - self._mean
+        tot = self._count + bc
+        self._var = (self._var * self._count + bv * bc + d * d * self._count * bc / tot) / tot
+        self._mean = self._mean + d * bc / tot
+        self._count = tot
+        self._m32.copy_(self._mean)
+        self._v32.copy_(self._var)
+        env.ext.wait_stream(torch_.cuda.current_stream(env.dev))
+        env.sim.policy_obs_norm_device(self._m32.data_ptr(), self._v32.data_ptr())
+        torch_.cuda.current_stream(env.dev).wait_stream(env.ext)
+
+    def iterate(self):
+        """One PPO iteration: rollout, (optional) ob_rms update, advantage estimation, update.  Returns
+        device tensors: the update's statistics rows [epochs * n_minibatch, 6] under 'stats' (columns
+        _lib.PPO_STATS) and the rollout's mean reward under 'mean_reward'; nothing is synchronised."""
+        h, env = self.hyper, self.env
+        out = env.rollout_policy(None, None, self.n_steps)
+        if h['update_ob_rms']:
+            # (the batch keeps the raw observations: the update normalises them with the new statistics)
+            self._update_ob_rms(out['obs'][:out['n']])
+        adv, ret = env.compute_gae(out, h['gamma'], h['lam'], h['bootstrap'])
+        stats = env.ppo_update(out, adv, ret, h, h['epochs'], h['n_minibatch'], generator=self.generator)
+        self.iterations += 1
+        self.last = dict(out=out, adv=adv, ret=ret)
+        return dict(stats=stats, mean_reward=out['rew'].mean())
+
+    def sync_module(self):
+        """Copy the device weights and observation statistics back into the torch module and ob_rms
+        (through avr_policy_get; blocks until the queued work is done)."""
+        d = self.env.sim.policy_get()
+        with torch.no_grad():
+            for k, p in module_params(self.actor_critic).items():
+                p.copy_(torch.as_tensor(d[k]).reshape(p.shape))
+        self.ob_rms.mean = np.asarray(d['ob_mean'], np.float64)
+        self.ob_rms.var = np.asarray(d['ob_var'], np.float64)
+        self.ob_rms.count = float(self._count)
+        return self.actor_critic, self.ob_rms
+
+    def save(self, path):
+        """sync_module, then policy_eval.save_policy: the checkpoint loads with load_policy and runs
+        in evaluate(..., fused=True)."""
+        self.sync_module()
+        PE.save_policy(path, self.actor_critic, self.ob_rms)

@@ -47,6 +47,19 @@
     int avr_rollover_device(avr_sim *s, const uint8_t *d_done, float *d_obs);                                      \
     int avr_rollover_buffers(avr_sim *s, float **d_term_obs, float **d_term_value, int32_t **d_episode);           \
     int avr_rollover_set_episodes(avr_sim *s, const int32_t *host_episode);                                        \
+    int avr_gae_device(avr_sim *s, int32_t n, float gamma, float lam, int32_t bootstrap, const float *d_rew,        \
+                       const uint8_t *d_done, const float *d_value, float *d_adv, float *d_ret);                   \
+    int avr_ppo_reset(avr_sim *s);                                                                                 \
+    int avr_ppo_grad_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t minibatch,         \
+                            int32_t n_minibatch, const int32_t *d_perm);                                           \
+    int avr_ppo_adam_device(avr_sim *s, const avr_ppo_params *p);                                                  \
+    int avr_ppo_update_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t epochs,          \
+                              int32_t n_minibatch, const int32_t *d_perm);                                         \
+    int avr_ppo_buffers(avr_sim *s, float **d_grad, float **d_m, float **d_v, float **d_stats);                    \
+    int32_t avr_ppo_words(void);                                                                                   \
+    void *avr_policy_block(avr_sim *s);                                                                            \
+    int avr_policy_get(avr_sim *s, avr_policy_out *out);                                                           \
+    int avr_policy_obs_norm_device(avr_sim *s, const float *d_mean, const float *d_var);                           \
     int avr_human_variants_set(avr_sim *s, int32_t n_var, const avr_human_variant *v);                             \
     int32_t avr_human_variants(avr_sim *s);                                                                        \
     int avr_human_variant_info(avr_sim *s, int32_t v, int32_t *gender, float *height);                             \
@@ -221,6 +234,26 @@ int avr_rollover_enable(avr_sim *s, int32_t on) { DISPATCH(s, avr_rollover_enabl
 int avr_rollover_device(avr_sim *s, const uint8_t *d, float *o) { DISPATCH(s, avr_rollover_device(h, d, o)); }
 int avr_rollover_buffers(avr_sim *s, float **to, float **tv, int32_t **ep) { DISPATCH(s, avr_rollover_buffers(h, to, tv, ep)); }
 int avr_rollover_set_episodes(avr_sim *s, const int32_t *ep) { DISPATCH(s, avr_rollover_set_episodes(h, ep)); }
+int avr_gae_device(avr_sim *s, int32_t n, float gamma, float lam, int32_t bootstrap, const float *r, const uint8_t *d, const float *v, float *adv,
+                   float *ret) {
+    DISPATCH(s, avr_gae_device(h, n, gamma, lam, bootstrap, r, d, v, adv, ret));
+}
+int avr_ppo_reset(avr_sim *s) { DISPATCH(s, avr_ppo_reset(h)); }
+int avr_ppo_grad_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t j, int32_t m, const int32_t *perm) {
+    DISPATCH(s, avr_ppo_grad_device(h, b, p, j, m, perm));
+}
+int avr_ppo_adam_device(avr_sim *s, const avr_ppo_params *p) { DISPATCH(s, avr_ppo_adam_device(h, p)); }
+int avr_ppo_update_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t epochs, int32_t m, const int32_t *perm) {
+    DISPATCH(s, avr_ppo_update_device(h, b, p, epochs, m, perm));
+}
+int avr_ppo_buffers(avr_sim *s, float **g, float **m, float **v, float **st) { DISPATCH(s, avr_ppo_buffers(h, g, m, v, st)); }
+int32_t avr_ppo_words(void) { return avr_feeding::avr_ppo_words(); }
+void *avr_policy_block(avr_sim *s) {
+    if (!s || !s->impl) return nullptr;
+    DISPATCH_ANY(s, avr_policy_block(h));
+}
+int avr_policy_get(avr_sim *s, avr_policy_out *o) { DISPATCH(s, avr_policy_get(h, o)); }
+int avr_policy_obs_norm_device(avr_sim *s, const float *m, const float *v) { DISPATCH(s, avr_policy_obs_norm_device(h, m, v)); }
 int avr_substep(avr_sim *s, float dt) { DISPATCH(s, avr_substep(h, dt)); }
 int avr_sync(avr_sim *s) { DISPATCH(s, avr_sync(h)); }
 int avr_kernel_info(avr_sim *s, int32_t *o) { DISPATCH(s, avr_kernel_info(h, o)); }

@@ -74,6 +74,17 @@ struct avr_sim {
     // address the rollout graphs' policy nodes hold, and the forward's own log-prob / value rows
     float *d_pol, *d_logp, *d_val;
     int pol_critic;                        // the installed policy has a critic
+    int pol_hidden, pol_norm;              // its hidden width; it has ob_rms rows
+    float pol_eps;                         // avr_policy_desc.eps of the last avr_policy_set
+    // the PPO update on the device (avr_ppo_reset, avr_ppo.hip): the gradient block and Adam's moments
+    // (the weight block's layout), the gradient kernel's per-block partials, the statistics rows, the
+    // advantage mean / std and the step count
+    float *d_ppo_grad, *d_ppo_m, *d_ppo_v, *d_ppo_part, *d_ppo_stats, *d_ppo_advstat;
+    double *d_ppo_spart, *d_ppo_advpart;
+    int *d_ppo_step;
+    int ppo_row;                           // the statistics row the last gradient call wrote
+    const float *ppo_adv;                  // the batch (adv pointer, sample count) whose advantage mean / std the
+    long long ppo_adv_n;                   //   device holds (NULL: none)
     // device-side episode rollover (avr_reset_pool_set, avr_rollover_*; avr_rollover.hip): the pool
     // block (header, pool_cap state rows, pool_cap observation rows), whose address the rollout
     // graphs of the rollover mode hold, and the per-env terminal observation / value / episode
@@ -1177,6 +1188,7 @@ int avr_policy_set(avr_sim *s, const avr_policy_desc *p) {
     HIPCHK(s, hipMemcpyAsync(s->d_pol, w.data(), PW_WORDS * sizeof(float), hipMemcpyHostToDevice, s->stream));
     HIPCHK(s, hipStreamSynchronize(s->stream));
     s->pol_critic = nc != 0;
+    s->pol_hidden = H; s->pol_norm = p->ob_mean != nullptr; s->pol_eps = p->eps;
     return 0;
 }
 
@@ -1294,6 +1306,194 @@ int avr_rollover_set_episodes(avr_sim *s, const int32_t *host_episode) {
     if (!host_episode) return fail(s, -1, "avr_rollover_set_episodes: host_episode is NULL");
     HIPCHK(s, hipMemcpyAsync(s->d_episode, host_episode, (size_t)s->cfg.n_envs * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
     HIPCHK(s, hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------ the PPO update on the device
+int avr_gae_device(avr_sim *s, int32_t n, float gamma, float lam, int32_t bootstrap, const float *d_rew, const uint8_t *d_done, const float *d_value,
+                   float *d_adv, float *d_ret) {
+    CHECK_SIM(s);
+    if (n < 1) return fail(s, -1, "avr_gae_device: n %d < 1", (int)n);
+    if (!d_rew || !d_done || !d_value || !d_adv || !d_ret) return fail(s, -1, "avr_gae_device: d_rew, d_done, d_value, d_adv and d_ret must be given");
+    if (bootstrap && !s->d_pool) return fail(s, -1, "avr_gae_device: bootstrap needs the rollover's terminal values (call avr_reset_pool_set first)");
+    if (bootstrap && n > s->km.max_steps)
+        return fail(s, -1, "avr_gae_device: bootstrap with n %d > %d steps per episode (only each env's most recent terminal value is kept)", (int)n,
+                    (int)s->km.max_steps);
+    HIPCHK(s, avr_launch_gae(d_rew, d_done, d_value, bootstrap ? s->d_term_val : nullptr, gamma, lam, n, s->cfg.n_envs, d_adv, d_ret, s->stream));
+    return 0;
+}
+
+int avr_ppo_reset(avr_sim *s) {
+    CHECK_SIM(s);
+    if (!s->d_pol) return fail(s, -1, "avr_ppo_reset: no policy (call avr_policy_set first)");
+    const size_t fw = 3 * (size_t)PW_WORDS + (size_t)PPO_MAX_BLOCKS * 2 * PPO_PART + (size_t)PPO_STATS_ROWS * PPO_STAT_WORDS + 8;
+    const size_t dw = (size_t)PPO_MAX_BLOCKS * 2 * PPO_STAT_WORDS + 2 * PPO_ADV_BLOCKS;
+    if (!s->d_ppo_grad) {
+        // one block: the doubles first (alignment), then the float rows, then the step count
+        double *blk = nullptr;
+        HIPCHK(s, hipMalloc(&blk, dw * sizeof(double) + fw * sizeof(float)));
+        s->allocs.push_back(blk);
+        s->d_ppo_spart = blk; s->d_ppo_advpart = blk + (size_t)PPO_MAX_BLOCKS * 2 * PPO_STAT_WORDS;
+        float *f = (float *)(blk + dw);
+        s->d_ppo_m = f + PW_WORDS; s->d_ppo_v = f + 2 * (size_t)PW_WORDS;
+        s->d_ppo_part = f + 3 * (size_t)PW_WORDS;
+        s->d_ppo_stats = s->d_ppo_part + (size_t)PPO_MAX_BLOCKS * 2 * PPO_PART;
+        s->d_ppo_advstat = s->d_ppo_stats + (size_t)PPO_STATS_ROWS * PPO_STAT_WORDS;
+        s->d_ppo_step = (int *)(s->d_ppo_advstat + 4);
+        s->d_ppo_grad = f;
+    }
+    HIPCHK(s, hipMemsetAsync(s->d_ppo_spart, 0, dw * sizeof(double) + fw * sizeof(float), s->stream));
+    s->ppo_row = 0;
+    s->ppo_adv = nullptr; s->ppo_adv_n = 0;
+    return 0;
+}
+
+static int ppo_check(avr_sim *s, const char *who, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t n_minibatch) {
+    if (!s->d_pol) return fail(s, -1, "%s: no policy (call avr_policy_set first)", who);
+    if (!s->d_ppo_grad) return fail(s, -1, "%s: no optimiser state (call avr_ppo_reset first)", who);
+    if (!p) return fail(s, -1, "%s: params is NULL", who);
+    if (!b) return 0;
+    if (!b->obs || !b->act || !b->logp || !b->adv) return fail(s, -1, "%s: the batch's obs, act, logp and adv must be given", who);
+    if (b->n < 1 || b->E < 1) return fail(s, -1, "%s: batch n %d / E %d < 1", who, (int)b->n, (int)b->E);
+    const long long N = (long long)b->n * b->E;
+    if (N > 0x7fffffffLL) return fail(s, -1, "%s: batch of %lld samples (int32 sample indices)", who, N);
+    if (n_minibatch < 1 || n_minibatch > N) return fail(s, -1, "%s: n_minibatch %d outside 1..%lld", who, (int)n_minibatch, N);
+    if (p->vf_coef != 0.f && !s->pol_critic) return fail(s, -1, "%s: vf_coef %g without a critic installed", who, (double)p->vf_coef);
+    if (s->pol_critic && (!b->ret || (p->clip_value && !b->value)))
+        return fail(s, -1, "%s: with a critic installed the batch's ret (and value, when the value loss is clipped) must be given", who);
+    if (!(p->clip >= 0.f)) return fail(s, -1, "%s: clip %g < 0", who, (double)p->clip);
+    return 0;
+}
+
+// one minibatch's gradient into d_grad and statistics row `row`; advstat: compute the batch's advantage mean / std
+// first (a single call's minibatch 0; the update loop's first minibatch: adv does not change between its epochs)
+static int ppo_grad(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t j, int32_t M, const int32_t *d_perm, int row, bool advstat) {
+    const long long N = (long long)b->n * b->E;
+    if (p->norm_adv && advstat) {
+        HIPCHK(s, avr_launch_ppo_advstat(b->adv, N, s->d_ppo_advpart, s->d_ppo_advstat, s->stream));
+        s->ppo_adv = b->adv; s->ppo_adv_n = N;
+    } else if (p->norm_adv && (s->ppo_adv != b->adv || s->ppo_adv_n != N)) {
+        return fail(s, -1, "avr_ppo_grad_device: minibatch %d with norm_adv before minibatch 0 of this batch (it computes the advantage statistics)", (int)j);
+    }
+    PpoArgs A;
+    A.obs = b->obs; A.act = b->act; A.logp = b->logp; A.value = b->value; A.adv = b->adv; A.ret = b->ret;
+    A.perm = d_perm; A.N = N; A.B = (int)(N / M); A.base = (long long)j * A.B;
+    A.clip = p->clip; A.vf_coef = p->vf_coef; A.inv_B = 1.f / (float)A.B;
+    A.norm_adv = p->norm_adv != 0; A.clip_value = p->clip_value != 0;
+    s->ppo_row = row % PPO_STATS_ROWS;
+    HIPCHK(s, avr_launch_ppo_grad(s->d_pol, A, p->ent_coef, s->d_ppo_advstat, s->d_ppo_part, s->d_ppo_spart, s->d_ppo_grad,
+                                  s->d_ppo_stats + (size_t)s->ppo_row * PPO_STAT_WORDS, s->stream));
+    return 0;
+}
+
+static int ppo_adam(avr_sim *s, const avr_ppo_params *p) {
+    if (!(p->eps > 0.f)) return fail(s, -1, "avr_ppo_adam_device: Adam's eps %g must be > 0", (double)p->eps);
+    const PpoAdam a = {p->max_grad_norm, p->lr, p->beta1, p->beta2, p->eps};
+    HIPCHK(s, avr_launch_ppo_adam(s->d_pol, s->d_ppo_grad, s->d_ppo_m, s->d_ppo_v, s->d_ppo_step, s->d_ppo_stats + (size_t)s->ppo_row * PPO_STAT_WORDS, a,
+                                  s->stream));
+    return 0;
+}
+
+int avr_ppo_grad_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t minibatch, int32_t n_minibatch, const int32_t *d_perm) {
+    CHECK_SIM(s);
+    if (!b) return fail(s, -1, "avr_ppo_grad_device: batch is NULL");
+    if (int r = ppo_check(s, "avr_ppo_grad_device", b, p, n_minibatch)) return r;
+    if (minibatch < 0 || minibatch >= n_minibatch) return fail(s, -1, "avr_ppo_grad_device: minibatch %d outside 0..%d", (int)minibatch, (int)n_minibatch - 1);
+    return ppo_grad(s, b, p, minibatch, n_minibatch, d_perm, minibatch, minibatch == 0);
+}
+
+int avr_ppo_adam_device(avr_sim *s, const avr_ppo_params *p) {
+    CHECK_SIM(s);
+    if (int r = ppo_check(s, "avr_ppo_adam_device", nullptr, p, 1)) return r;
+    return ppo_adam(s, p);
+}
+
+int avr_ppo_update_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t epochs, int32_t n_minibatch, const int32_t *d_perm) {
+    CHECK_SIM(s);
+    if (!b) return fail(s, -1, "avr_ppo_update_device: batch is NULL");
+    if (int r = ppo_check(s, "avr_ppo_update_device", b, p, n_minibatch)) return r;
+    if (epochs < 1) return fail(s, -1, "avr_ppo_update_device: epochs %d < 1", (int)epochs);
+    if (!(p->eps > 0.f)) return fail(s, -1, "avr_ppo_update_device: Adam's eps %g must be > 0", (double)p->eps);
+    const long long N = (long long)b->n * b->E;
+    for (int32_t ep = 0; ep < epochs; ep++)
+        for (int32_t j = 0; j < n_minibatch; j++) {
+            if (int r = ppo_grad(s, b, p, j, n_minibatch, d_perm ? d_perm + (size_t)ep * N : nullptr, ep * n_minibatch + j, ep == 0 && j == 0))
+                return r;
+            if (int r = ppo_adam(s, p)) return r;
+        }
+    return 0;
+}
+
+int avr_ppo_buffers(avr_sim *s, float **d_grad, float **d_m, float **d_v, float **d_stats) {
+    CHECK_SIM(s);
+    if (!s->d_ppo_grad) return fail(s, -1, "avr_ppo_buffers: no optimiser state (call avr_ppo_reset first)");
+    if (d_grad) *d_grad = s->d_ppo_grad;
+    if (d_m) *d_m = s->d_ppo_m;
+    if (d_v) *d_v = s->d_ppo_v;
+    if (d_stats) *d_stats = s->d_ppo_stats;
+    return 0;
+}
+
+int32_t avr_ppo_words(void) { return PW_WORDS; }
+void *avr_policy_block(avr_sim *s) { return s ? s->d_pol : nullptr; }
+
+int avr_policy_get(avr_sim *s, avr_policy_out *o) {
+    CHECK_SIM(s);
+    if (!s->d_pol) return fail(s, -1, "avr_policy_get: no policy (call avr_policy_set first)");
+    if (!o) return fail(s, -1, "avr_policy_get: out is NULL");
+    std::vector<float> w(PW_WORDS);
+    HIPCHK(s, hipMemcpyAsync(w.data(), s->d_pol, PW_WORDS * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    const int H = s->pol_hidden;
+    o->hidden = H; o->has_ob_rms = s->pol_norm; o->has_critic = s->pol_critic; o->clip_obs = w[PW_HDR + 2]; o->eps = s->pol_eps;
+    if (s->pol_norm)
+        for (int k = 0; k < K_OBS_DIM; k++) {
+            if (o->ob_mean) o->ob_mean[k] = w[PW_MEAN + k];
+            if (!o->ob_var) continue;
+            // a float variance that avr_policy_set's (float)sqrt((double)var + eps) maps back to this divisor
+            const float sd = w[PW_SD + k];
+            float var = (float)((double)sd * (double)sd - (double)s->pol_eps);
+            for (int it = 0; it < 8; it++) {
+                const float back = (float)std::sqrt((double)var + (double)s->pol_eps);
+                if (back == sd) break;
+                var = std::nextafter(var, back < sd ? INFINITY : -INFINITY);
+            }
+            // (rounding around eps can leave a variance of about 0 slightly negative: 0 where that is the same divisor)
+            if (var < 0.f && (float)std::sqrt((double)s->pol_eps) == sd) var = 0.f;
+            o->ob_var[k] = var;
+        }
+    for (int a = 0; a < K_ACT_DIM; a++) {
+        if (o->logstd) o->logstd[a] = w[PW_LOGSTD + a];
+        if (o->mu_b) o->mu_b[a] = w[PW_BH + a];
+        if (o->mu_w)
+            for (int k = 0; k < H; k++) o->mu_w[a * H + k] = w[PW_WH + k * 8 + a];
+    }
+    if (s->pol_critic) {
+        if (o->c_b3) o->c_b3[0] = w[PW_BH + 7];
+        if (o->c_w3)
+            for (int k = 0; k < H; k++) o->c_w3[k] = w[PW_WH + k * 8 + 7];
+    }
+    for (int net = 0; net < (s->pol_critic ? 2 : 1); net++) {
+        const float *wn = w.data() + PW_NET + net * PN_WORDS;
+        float *w1 = net ? o->c_w1 : o->a_w1, *b1 = net ? o->c_b1 : o->a_b1, *w2 = net ? o->c_w2 : o->a_w2, *b2 = net ? o->c_b2 : o->a_b2;
+        for (int j = 0; j < H; j++) {
+            if (b1) b1[j] = wn[PN_B1 + j];
+            if (b2) b2[j] = wn[PN_B2 + j];
+            if (w1)
+                for (int k = 0; k < K_OBS_DIM; k++) w1[j * K_OBS_DIM + k] = wn[PN_W1 + k * POL_H + j];
+            if (w2)
+                for (int k = 0; k < H; k++) w2[j * H + k] = wn[PN_W2 + k * POL_H + j];
+        }
+    }
+    return 0;
+}
+
+int avr_policy_obs_norm_device(avr_sim *s, const float *d_mean, const float *d_var) {
+    CHECK_SIM(s);
+    if (!s->d_pol) return fail(s, -1, "avr_policy_obs_norm_device: no policy (call avr_policy_set first)");
+    if (!s->pol_norm) return fail(s, -1, "avr_policy_obs_norm_device: the installed policy has no ob_rms");
+    if (!d_mean || !d_var) return fail(s, -1, "avr_policy_obs_norm_device: d_mean and d_var must be given");
+    HIPCHK(s, avr_launch_obs_norm(s->d_pol, d_mean, d_var, s->pol_eps, s->stream));
     return 0;
 }
 

@@ -906,6 +906,31 @@ int avr_rollover_set_episodes(avr_sim *s, const int32_t *host_episode) {
     (void)host_episode;
     return fail(s, -1, "device rollover: not built for DressingJaco");
 }
+// (the PPO update works on the device policy's weight block, avr_ppo.hip)
+#define DRESS_NO_PPO return fail(s, -1, "PPO update: not built for DressingJaco")
+int avr_gae_device(avr_sim *s, int32_t n, float gamma, float lam, int32_t bootstrap, const float *d_rew, const uint8_t *d_done, const float *d_value,
+                   float *d_adv, float *d_ret) {
+    (void)n; (void)gamma; (void)lam; (void)bootstrap; (void)d_rew; (void)d_done; (void)d_value; (void)d_adv; (void)d_ret;
+    DRESS_NO_PPO;
+}
+int avr_ppo_reset(avr_sim *s) { DRESS_NO_PPO; }
+int avr_ppo_grad_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t minibatch, int32_t n_minibatch, const int32_t *d_perm) {
+    (void)b; (void)p; (void)minibatch; (void)n_minibatch; (void)d_perm;
+    DRESS_NO_PPO;
+}
+int avr_ppo_adam_device(avr_sim *s, const avr_ppo_params *p) { (void)p; DRESS_NO_PPO; }
+int avr_ppo_update_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t epochs, int32_t n_minibatch, const int32_t *d_perm) {
+    (void)b; (void)p; (void)epochs; (void)n_minibatch; (void)d_perm;
+    DRESS_NO_PPO;
+}
+int avr_ppo_buffers(avr_sim *s, float **d_grad, float **d_m, float **d_v, float **d_stats) {
+    (void)d_grad; (void)d_m; (void)d_v; (void)d_stats;
+    DRESS_NO_PPO;
+}
+int32_t avr_ppo_words(void) { return 0; }
+void *avr_policy_block(avr_sim *s) { (void)s; return nullptr; }
+int avr_policy_get(avr_sim *s, avr_policy_out *out) { (void)out; DRESS_NO_PPO; }
+int avr_policy_obs_norm_device(avr_sim *s, const float *d_mean, const float *d_var) { (void)d_mean; (void)d_var; DRESS_NO_PPO; }
 int avr_step(avr_sim *s, const float *act, float *obs, float *rew, uint8_t *done, float *info) {
     CHECK_SIM(s);
     const size_t E = (size_t)s->cfg.n_envs;

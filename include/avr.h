@@ -199,6 +199,106 @@ int avr_rollover_buffers(avr_sim *sim, float **d_term_obs, float **d_term_value,
  *   resets and device rollovers; blocks until done). */
 int avr_rollover_set_episodes(avr_sim *sim, const int32_t *host_episode);
 
+/* ---- the PPO update on the device (FeedingJaco, ScratchItchPR2, BedBathingPR2; DressingJaco: -1) ----
+ * The consumer of avr_rollout_policy_device's batch: advantage estimation, the clipped-surrogate loss of
+ * a2c_ppo_acktr's PPO.update with its backward through both networks, gradient clipping and Adam, writing
+ * the handle's weight block in place in stream order on avr_stream(sim) -- the next rollout's graphs read
+ * the new weights with no re-capture and no host work (csrc/avr_ppo.hip; no reference counterpart: the
+ * reference ships neither its trainer nor a2c_ppo_acktr).  No float atomics: the same call on the same
+ * inputs gives the same bits.  avr/ppo.py gae_reference / ppo_loss_reference are the readable mirrors.
+ *
+ * avr_gae_device: generalised advantage estimation over stacked device arrays d_rew[n][n_envs],
+ *   d_done[n][n_envs], d_value[n+1][n_envs] into d_adv[n][n_envs], d_ret[n][n_envs], k = n-1 .. 0 per env in
+ *   plain fp32 multiplies and adds in exactly this order:
+ *     nv    = done[k] ? (bootstrap ? term_value[e] : 0) : value[k+1][e]
+ *     delta = (rew[k] + gamma * nv) - value[k]
+ *     gae   = delta + (gamma * lam) * (done[k] ? 0 : gae);   adv[k] = gae;  ret[k] = gae + value[k]
+ *   Every done here is the TimeLimit: bootstrap = 1 treats it as a truncation and bootstraps from the
+ *   handle's d_term_value row (avr_rollover_buffers; an error before avr_reset_pool_set), bootstrap = 0 cuts
+ *   the return there, as a2c_ppo_acktr does by default.  The handle keeps only each env's most recent
+ *   terminal value, so bootstrap = 1 with n > max_episode_steps (an env could finish twice) is an error. */
+int avr_gae_device(avr_sim *sim, int32_t n, float gamma, float lam, int32_t bootstrap, const float *d_rew, const uint8_t *d_done,
+                   const float *d_value, float *d_adv, float *d_ret);
+/* A batch of N = n * E samples in device arrays, flattened [n][E] as the rollout stacks them (E need not be
+ * the handle's n_envs): obs rows of obs_dim raw observations (the kernel normalises them with the weight
+ * block's current ob_rms rows and clip, as the forward does; a rollout's [n+1][E] array is fine, the last
+ * slot is not read), act rows of act_dim, logp / value the rollout's (value may be [n+1][E]), adv / ret
+ * avr_gae_device's. */
+typedef struct avr_ppo_batch {
+    int32_t n, E;
+    const float *obs, *act, *logp, *value, *adv, *ret;
+} avr_ppo_batch;
+typedef struct avr_ppo_params {
+    float clip;                     /* c of the ratio clip and of the value clip                    */
+    float vf_coef, ent_coef;        /* L = L_pi + vf_coef L_v - ent_coef H                           */
+    float max_grad_norm;            /* global L2 clip (<= 0: none)                                   */
+    float lr, beta1, beta2, eps;    /* Adam (eps > 0)                                                */
+    int32_t norm_adv;               /* use (adv - mean) / (std + 1e-5), mean / std over the batch    */
+    int32_t clip_value;             /* the clipped value loss (0: 0.5 mean (v - ret)^2)               */
+} avr_ppo_params;
+#define AVR_PPO_STAT_WORDS 8
+#define AVR_PPO_STATS_ROWS 256
+/* avr_ppo_reset: allocate (first call) and zero Adam's moments m, v (two blocks of the weight block's
+ *   layout), the step count, the gradient block, the partials and the statistics rows.  An error before
+ *   avr_policy_set.
+ * avr_ppo_grad_device: the gradient of minibatch `minibatch` of n_minibatch: B = N / n_minibatch samples
+ *   (the remainder is dropped), sample i of it is d_perm[minibatch * B + i] (d_perm: device int32[N] with
+ *   entries in [0, N) -- an entry outside is clamped into the batch, not reported, so that nothing outside
+ *   the batch is ever read; NULL: the identity).  Called with minibatch == 0 it first computes the batch's
+ *   advantage mean and (unbiased) standard deviation, in double in a fixed tree, and keeps them on the
+ *   device for the following minibatches (norm_adv with minibatch != 0 before minibatch 0 of the same adv
+ *   array and sample count is an error).  Per sample, with mean / logstd / v the networks' outputs:
+ *     logp_new = sum_a -(act_a - mean_a)^2 / (2 exp(2 logstd_a)) - logstd_a - log(2 pi) / 2
+ *     ratio = exp(logp_new - logp);  L_pi = -mean(min(ratio A, clamp(ratio, 1 - c, 1 + c) A))
+ *     v_clip = value + clamp(v - value, -c, c);  L_v = 0.5 mean(max((v - ret)^2, (v_clip - ret)^2))
+ *     H = sum_a (0.5 + log(2 pi) / 2 + logstd_a);  L = L_pi + vf_coef L_v - ent_coef H
+ *   d_grad (the weight block's layout; zero in the header and ob_rms rows and in all zero padding) receives
+ *   dL / d(every weight, bias and logstd), and statistics row (minibatch % AVR_PPO_STATS_ROWS) of d_stats
+ *   {L_pi, L_v, H, approx_kl = mean(logp - logp_new), clip_frac = mean(|ratio - 1| > c), grad_norm, -, -}
+ *   (grad_norm by the next avr_ppo_adam_device).  vf_coef != 0 without a critic installed is an error.
+ * avr_ppo_adam_device: the global L2 norm of d_grad (in double), d_grad * min(1, max_grad_norm / (norm +
+ *   1e-6)), then bias-corrected Adam (torch.optim.Adam's formulas; the step count lives on the device) on
+ *   the weight block in place.  Separate from the gradient call so that a caller can read or all-reduce
+ *   d_grad in between.
+ * avr_ppo_update_device: for every epoch, for every minibatch: the two calls above, with no host
+ *   synchronisation and bit-identical to calling them one by one; d_perm is [epochs][N] (NULL: the
+ *   identity each epoch); the advantage statistics are computed once, before the first minibatch;
+ *   statistics row (epoch * n_minibatch + minibatch) % AVR_PPO_STATS_ROWS.
+ * avr_ppo_buffers: device pointers owned by the handle (any may be NULL): d_grad, d_m, d_v (weight block
+ *   layout, avr_ppo_words() floats each) and d_stats[AVR_PPO_STATS_ROWS][AVR_PPO_STAT_WORDS].
+ * All are asynchronous on avr_stream(sim); all but avr_ppo_reset are errors before it. */
+int avr_ppo_reset(avr_sim *sim);
+int avr_ppo_grad_device(avr_sim *sim, const avr_ppo_batch *batch, const avr_ppo_params *params, int32_t minibatch, int32_t n_minibatch,
+                        const int32_t *d_perm);
+int avr_ppo_adam_device(avr_sim *sim, const avr_ppo_params *params);
+int avr_ppo_update_device(avr_sim *sim, const avr_ppo_batch *batch, const avr_ppo_params *params, int32_t epochs, int32_t n_minibatch,
+                          const int32_t *d_perm);
+int avr_ppo_buffers(avr_sim *sim, float **d_grad, float **d_m, float **d_v, float **d_stats);
+/* Floats in the weight block (and in d_grad, d_m, d_v), and the block's device address (NULL before
+ * avr_policy_set); the layout is csrc/avr_policy.hip's PW_* (avr/ppo.py mirrors it: the PW_* / PN_*
+ * constants, block_live_mask, unpack_block). */
+int32_t avr_ppo_words(void);
+void *avr_policy_block(avr_sim *sim);
+/* avr_policy_get: the inverse of avr_policy_set's packing: the weight block back into host arrays [out][in]
+ *   of the installed policy's dimensions (blocks until done).  Any pointer may be NULL; the critic's arrays
+ *   are left untouched without a critic, ob_mean / ob_var without ob_rms.  ob_var is a float for which
+ *   avr_policy_set's sqrt(var + eps) gives back the block's divisor bit for bit, so re-installing what this
+ *   call returned reproduces the block.  hidden, has_ob_rms, has_critic, clip_obs and eps are filled in. */
+typedef struct avr_policy_out {
+    int32_t hidden, has_ob_rms, has_critic;
+    float clip_obs, eps;
+    float *ob_mean, *ob_var;
+    float *a_w1, *a_b1, *a_w2, *a_b2;
+    float *mu_w, *mu_b, *logstd;
+    float *c_w1, *c_b1, *c_w2, *c_b2, *c_w3, *c_b3;
+} avr_policy_out;
+int avr_policy_get(avr_sim *sim, avr_policy_out *out);
+/* avr_policy_obs_norm_device: rewrite the block's ob_rms rows from device arrays d_mean[obs_dim],
+ *   d_var[obs_dim] in stream order: mean, and sqrt(var + eps) with the eps of the last avr_policy_set (a
+ *   trainer keeps VecNormalize's running statistics without a host round trip).  An error if the installed
+ *   policy has no ob_rms. */
+int avr_policy_obs_norm_device(avr_sim *sim, const float *d_mean, const float *d_var);
+
 /* ---- human height variants inside one handle (FeedingJaco, ScratchItchPR2, BedBathingPR2; DressingJaco: -1) ----
  * The reference's *New-v0 ids draw a new hipbone_to_mouth_height at every reset (feeding.py:170-172) and
  * rebuild the human (human_creation.py); here a handle holds a finite set of height variants and every env

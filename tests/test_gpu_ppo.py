@@ -1,0 +1,548 @@
+"""GPU: the PPO update on the device (csrc/avr_ppo.hip, include/avr.h avr_gae_device / avr_ppo_*):
+advantage estimation bit for bit against its float32 mirror, the minibatch gradient and the Adam
+steps against torch float64 autograd, the zero padding, determinism, the rollout reading the updated
+weights with no re-capture, the trainer end to end and the error paths."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from test_policy_host import random_policy
+from test_ppo_host import done_pattern, small_batch
+
+pytestmark = pytest.mark.gpu
+
+PARAMS = dict(clip=0.2, vf_coef=0.5, ent_coef=0.01, max_grad_norm=0.5, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-5, norm_adv=True, clip_value=True)
+KEYS = ('a_w1', 'a_b1', 'a_w2', 'a_b2', 'mu_w', 'mu_b', 'logstd', 'c_w1', 'c_b1', 'c_w2', 'c_b2', 'c_w3', 'c_b3')
+
+
+@pytest.fixture(scope='module')
+def feeding(scene):
+    """(A, md, 16 FeedingJaco reset states) shared by the tests of this module; never modified."""
+    from avr import _lib, reset as RS
+    _lib.load()
+    A, md = scene
+    S, _ = RS.batch_reset_states_fast(A, md, 1001, list(range(16)), impairment='random')
+    S = S.astype(np.float32)
+    S.setflags(write=False)
+    return A, md, S
+
+
+def dev_tensor(ptr, shape, typestr='<f4'):
+    """A torch tensor over device memory the handle owns (no copy)."""
+    import torch
+    holder = type('_DevArray', (), {})()
+    holder.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2, strides=None)
+    return torch.as_tensor(holder, device='cuda')
+
+
+def policy32(obs_dim, hidden, seed, ob_rms=True):
+    """random_policy with ob_rms rounded to float32 values (what the device block holds)."""
+    pol, rms = random_policy(obs_dim, 7, hidden, seed=seed)
+    rms.mean = rms.mean.astype(np.float32).astype(np.float64)
+    rms.var = rms.var.astype(np.float32).astype(np.float64)
+    return pol, (rms if ob_rms else None)
+
+
+def make_batch(pol, rms, N, seed):
+    """test_ppo_host.small_batch (ratios on both sides of 1 +- c, values on both sides of the value
+    clip) with observation components pushed beyond +-clip_obs after normalisation."""
+    b = small_batch(pol, rms, N, seed)
+    if rms is not None:
+        b['obs'][::3, 4] += 40.0
+        b['obs'][1::5, 17] -= 55.0
+    return b
+
+
+def make_sim(md, n=8, **kw):
+    from avr import _lib
+    return _lib.Sim(md, n, **kw)
+
+
+def install(sim, pol, rms):
+    from avr import policy_eval as PE
+    d = PE.policy_desc(pol, rms, sim.obs_dim, 7)
+    sim.policy_set(d)
+    sim.ppo_reset()
+    return d
+
+
+def upload(sim, batch, n=None):
+    """(avr_ppo_batch, the device tensors it points to) of a flattened host batch as n x (N / n)."""
+    import torch
+    N = len(batch['adv'])
+    n = 1 if n is None else n
+    T = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in batch.items()}
+    torch.cuda.synchronize()
+    return sim.ppo_batch(n, N // n, **{k: T[k].data_ptr() for k in T}), T
+
+
+def block(sim, which):
+    """Host copy of the weight block ('w') or of the gradient / m / v block."""
+    sim.sync()
+    ptr = sim.policy_block() if which == 'w' else sim.ppo_buffers()['gmv'.index(which)]
+    return dev_tensor(ptr, (sim.ppo_words(),)).cpu().numpy().copy()
+
+
+def stats_row(sim, row):
+    sim.sync()
+    return dev_tensor(sim.ppo_buffers()[3], (256, 8)).cpu().numpy()[row].copy()
+
+
+def reference_grads(pol, rms, batch, idx, params, dtype):
+    """({key: gradient array}, statistics) of ppo_loss_reference by torch CPU autograd in dtype."""
+    import copy
+    import torch
+    from avr import ppo
+    p = copy.deepcopy(pol).to(dtype)
+    b = {k: torch.from_numpy(v).to(dtype) for k, v in batch.items()}
+    loss, st = ppo.ppo_loss_reference(p, rms, b, None if idx is None else torch.as_tensor(idx, dtype=torch.long), params)
+    named = ppo.module_params(p)
+    g = torch.autograd.grad(loss, [named[k] for k in KEYS])
+    return {k: x.numpy().astype(np.float64) for k, x in zip(KEYS, g)}, {k: float(v) for k, v in st.items()}
+
+
+U32 = 2.0 ** -23                             # one float32 ulp, relative
+
+
+def check_8x(what, dev, t32, r64, floor=None):
+    """The project's tolerance rule (tests/test_gpu_policy.py) on each of the 13 parameter tensors:
+    the device's max error against float64 is at most 8 x the error of torch's CPU float32 run
+    against the same float64.  floor: {tensor: absolute error} for a one-element tensor only (c_b3),
+    where torch's error is a single draw that can land arbitrarily close to zero (9.6e-10 was seen
+    on a 0.059 gradient whose other summation orders give about 1e-8): there the bound is the larger
+    of the rule's and the floor, which the caller derives from float32 rounding alone."""
+    bad = []
+    for k in KEYS:
+        bound = 8 * float(np.abs(t32[k] - r64[k]).max())
+        if floor and k in floor:
+            assert r64[k].size == 1
+            bound = max(bound, float(floor[k]))
+        err = float(np.abs(np.asarray(dev[k], np.float64) - r64[k]).max())
+        print('%s %s: bound %.3g observed %.3g (max |ref| %.3g)' % (what, k, bound, err, float(np.abs(r64[k]).max())))
+        if not (np.all(np.isfinite(dev[k])) and err <= bound):
+            bad.append((k, err, bound))
+    assert not bad, bad
+
+
+def value_bias_floor(pol, rms, batch, idx, params):
+    """The floor of c_b3's gradient error: one float32 ulp of the magnitude its sum accumulates.
+    d L / d c_b3 = sum_s t_s, t_s = (vf_coef / B) dL_v/dv_s with dL_v/dv_s = v_s - ret_s (or the clipped
+    form, same operands).  v_s = c_b3 + sum_k c_w3[k] h2_s[k] is itself a float32 dot product whose
+    rounding is relative to A_s = |c_b3| + sum_k |c_w3[k] h2_s[k]|, not to |v_s|, and the subtraction
+    cancels against |ret_s|; so every evaluation in float32, in any order, carries errors of the order
+    of 2^-24 (A_s + |ret_s|) vf_coef / B per term.  One ulp, 2^-23, of sum_s (A_s + |ret_s|) vf_coef / B
+    allows two such roundings per term and nothing else; it does not depend on the code under test."""
+    import copy
+    import torch
+    from avr import policy_eval as PE
+    p = copy.deepcopy(pol).double()
+    with torch.no_grad():
+        x = torch.from_numpy(batch['obs'][idx]).double()
+        if rms is not None:
+            x = PE.normalize(x, rms)
+        c = list(p.critic)
+        h2 = torch.nn.Sequential(*c[:4])(x)
+        A = c[4].bias.abs() + (h2 * c[4].weight[0]).abs().sum(-1)
+        ret = torch.from_numpy(batch['ret'][idx]).double().abs()
+    return U32 * float((A + ret).sum()) * params['vf_coef'] / len(idx)
+
+
+# ------------------------------------------------------------------ 1. advantage estimation
+def test_gae_bit_exact(feeding):
+    """n = 5, E = 70 (tail lanes live), done at k = 0, a middle k and k = n-1, both bootstrap modes:
+    the kernel equals the float32 numpy mirror bit for bit; bootstrap with n > the episode length
+    is rejected."""
+    import torch
+    from avr import ppo
+    A, md, S = feeding
+    n, E = 5, 70
+    rng = np.random.default_rng(7)
+    rew = rng.normal(0, 0.5, (n, E)).astype(np.float32)
+    value = rng.normal(0, 1.0, (n + 1, E)).astype(np.float32)
+    tv = rng.normal(0, 1.0, E).astype(np.float32)
+    done = np.tile(done_pattern(n, 7), (1, 10))
+    sim = make_sim(md, E)
+    t = {k: torch.from_numpy(v).cuda() for k, v in dict(rew=rew, value=value, done=done).items()}
+    adv, ret = torch.zeros(n, E, device='cuda'), torch.zeros(n, E, device='cuda')
+    torch.cuda.synchronize()
+    call = lambda n_, boot: sim.gae_device(n_, 0.99, 0.95, boot, t['rew'].data_ptr(), t['done'].data_ptr(), t['value'].data_ptr(), adv.data_ptr(),
+                                           ret.data_ptr())
+    with pytest.raises(RuntimeError, match='avr_reset_pool_set first'):
+        call(n, True)
+    sim.set_state(np.tile(S, (5, 1))[:E])
+    O = sim.settle(0)
+    sim.reset_pool_set(np.tile(S, (5, 1))[:4], O[:4])
+    dev_tensor(sim.rollover_buffers()[1], (E,)).copy_(torch.from_numpy(tv).cuda())
+    torch.cuda.synchronize()
+    for boot in (False, True):
+        call(n, boot)
+        sim.sync()
+        a_ref, r_ref = ppo.gae_reference(rew, done, value, tv, 0.99, 0.95, boot)
+        assert np.array_equal(adv.cpu().numpy(), a_ref) and np.array_equal(ret.cpu().numpy(), r_ref), boot
+    ms = int(md.params['max_episode_steps'])
+    big, o1, o2 = torch.zeros(ms + 2, E, device='cuda'), torch.zeros(ms + 1, E, device='cuda'), torch.zeros(ms + 1, E, device='cuda')
+    bd = torch.zeros(ms + 1, E, dtype=torch.uint8, device='cuda')
+    torch.cuda.synchronize()
+    with pytest.raises(RuntimeError, match='most recent terminal value'):
+        sim.gae_device(ms + 1, 0.99, 0.95, True, big.data_ptr(), bd.data_ptr(), big.data_ptr(), o1.data_ptr(), o2.data_ptr())
+    sim.gae_device(ms + 1, 0.99, 0.95, False, big.data_ptr(), bd.data_ptr(), big.data_ptr(), o1.data_ptr(), o2.data_ptr())   # (cut returns: any n)
+    sim.sync()
+    with pytest.raises(RuntimeError, match='n 0 < 1'):
+        call(0, False)
+    sim.close()
+
+
+# ------------------------------------------------------------------ 2. the gradient
+# The kernel takes 8 samples per wavefront pass and launches min(ceil(B / 8), 512) blocks per
+# network: 1 (a single live row), 8 (one full pass), 9 (a second block with one live row), 70 (9
+# blocks, a ragged last one); 8221 = 2 * 8 * 512 + 29 is the smallest kind of size at which blocks
+# loop (two full grid-strides), some take a third pass and the last pass is ragged (5 live rows).
+GRAD_CASES = {
+    'B1': dict(N=16, M=16, j=5), 'B8': dict(N=16, M=2, j=1), 'B9': dict(N=18, M=2, j=0), 'B70': dict(N=70, M=1, j=0),
+    'B8221': dict(N=8221, M=1, j=0),
+    'perm': dict(N=70, M=1, j=0, perm=True), 'M3of100': dict(N=100, M=3, j=1, perm=True),
+    'hidden40': dict(N=70, M=1, j=0, hidden=40), 'no_ob_rms': dict(N=70, M=1, j=0, ob_rms=False),
+}
+
+
+@pytest.mark.parametrize('case', list(GRAD_CASES))
+def test_gradient_matches_float64_autograd(feeding, case):
+    """Every parameter tensor's gradient of one minibatch against torch float64 autograd of
+    ppo_loss_reference, under the 8 x rule against torch's CPU float32 autograd.  The batch has
+    observations beyond +-clip_obs, ratios on both sides of 1 +- c and values beyond the value clip.
+    The L_pi / L_v / H / approx_kl / clip_frac statistics: 1e-5 absolute + 1e-5 relative (float32
+    evaluation of O(1) quantities, double accumulation); clip_frac exactly unless a ratio lies
+    within float32 rounding of the clip edge (none does here).
+    Observed on an MI355X, the tensor closest to its bound per case (observed / bound): B1 c_b1 8.8e-8 /
+    3.2e-7, B8 logstd 7.9e-7 / 2.3e-6, B9 c_b2 6.0e-8 / 3.1e-7, B70 c_w1 9.2e-8 / 4.8e-7, B8221 a_b2
+    4.0e-7 / 2.7e-6, perm c_b1 1.8e-8 / 7.0e-8, M3of100 c_w3 6.6e-8 / 4.2e-7, hidden40 a_w1 9.4e-7 /
+    4.2e-6, no_ob_rms logstd 3.2e-7 / 1.3e-6: at most 0.34 of the bound.  c_b3 (observed / its floor):
+    B1 7.6e-8, B8 6.9e-9, B9 8.2e-8, B70 3.4e-8, B8221 6.7e-9, perm 3.0e-8, M3of100 1.7e-8, no_ob_rms
+    1.5e-8, all / 6.7e-7 .. 8.0e-7; hidden40 1.5e-9 / 4.5e-7."""
+    A, md, _ = feeding
+    c = GRAD_CASES[case]
+    pol, rms = policy32(25, c.get('hidden', 64), seed=21, ob_rms=c.get('ob_rms', True))
+    batch = make_batch(pol, rms, c['N'], seed=22)
+    N, M, j = c['N'], c['M'], c['j']
+    B = N // M
+    perm = np.random.default_rng(23).permutation(N).astype(np.int32) if c.get('perm') else np.arange(N, dtype=np.int32)
+    idx = perm[j * B:(j + 1) * B].astype(np.int64)
+    import torch
+    r64, s64 = reference_grads(pol, rms, batch, idx, PARAMS, torch.float64)
+    t32, _ = reference_grads(pol, rms, batch, idx, PARAMS, torch.float32)
+    sim = make_sim(md)
+    install(sim, pol, rms)
+    pb, keep = upload(sim, batch)
+    dperm = torch.from_numpy(perm).cuda() if c.get('perm') else None
+    torch.cuda.synchronize()
+    for jj in sorted({0, j}):                 # (minibatch 0 computes the batch's advantage statistics)
+        sim.ppo_grad_device(pb, sim.ppo_params(PARAMS), jj, M, None if dperm is None else dperm.data_ptr())
+    from avr import ppo
+    g = block(sim, 'g')
+    st = stats_row(sim, j)
+    sim.close()
+    dev = ppo.unpack_block(g, 25, 7, pol.hidden)
+    assert np.all(g[~ppo.block_live_mask(25, 7, pol.hidden)] == 0)          # header, ob_rms rows and padding: exactly zero
+    check_8x('grad[%s]' % case, dev, t32, r64, floor=dict(c_b3=value_bias_floor(pol, rms, batch, idx, PARAMS)))
+    for i, k in enumerate(('policy_loss', 'value_loss', 'entropy', 'approx_kl', 'clip_frac')):
+        print('stat[%s] %s: device %.9g reference %.9g' % (case, k, st[i], s64[k]))
+        assert abs(st[i] - s64[k]) <= 1e-5 + 1e-5 * abs(s64[k]), (k, st[i], s64[k])
+
+
+# ------------------------------------------------------------------ 3. padding
+def test_padding_stays_zero(feeding):
+    """A 40-unit policy, three Adam steps at lr = 1e-2: every padded word of the weight block, of m
+    and of v is still exactly 0.0 (and the live words moved)."""
+    import torch
+    from avr import ppo
+    A, md, _ = feeding
+    pol, rms = policy32(25, 40, seed=31)
+    batch = make_batch(pol, rms, 70, seed=32)
+    sim = make_sim(md)
+    install(sim, pol, rms)
+    w0 = block(sim, 'w')
+    pb, keep = upload(sim, batch)
+    sim.ppo_update_device(pb, sim.ppo_params(dict(PARAMS, lr=1e-2)), 3, 1)
+    live = ppo.block_live_mask(25, 7, 40)
+    pad = ~live
+    pad[:ppo.PW_LOGSTD] = False
+    w, m, v = block(sim, 'w'), block(sim, 'm'), block(sim, 'v')
+    sim.close()
+    assert pad.sum() > 4000
+    for name, x in (('w', w), ('m', m), ('v', v)):
+        assert np.all(x[pad] == 0.0), name
+    assert np.array_equal(w[:ppo.PW_LOGSTD], w0[:ppo.PW_LOGSTD])             # header and ob_rms rows untouched
+    assert np.all(w[live] != w0[live]) and np.all(v[live] > 0)
+
+
+# ------------------------------------------------------------------ 4. Adam and clipping
+def torch_update(pol, rms, batch, params, epochs, M, dtype):
+    """epochs x M {loss; backward; clip_grad_norm_; Adam.step} on a copy of pol in dtype (identity
+    permutation); returns ({key: weights}, [statistics per minibatch])."""
+    import copy
+    import torch
+    from avr import ppo
+    p = copy.deepcopy(pol).to(dtype)
+    b = {k: torch.from_numpy(v).to(dtype) for k, v in batch.items()}
+    opt = torch.optim.Adam(p.parameters(), lr=params['lr'], betas=(params['beta1'], params['beta2']), eps=params['eps'])
+    N = len(batch['adv'])
+    B = N // M
+    rows = []
+    for ep in range(epochs):
+        for j in range(M):
+            opt.zero_grad()
+            loss, st = ppo.ppo_loss_reference(p, rms, b, torch.arange(j * B, (j + 1) * B), params)
+            loss.backward()
+            st['grad_norm'] = torch.nn.utils.clip_grad_norm_(p.parameters(), params['max_grad_norm'])
+            opt.step()
+            rows.append({k: float(v) for k, v in st.items()})
+    named = ppo.module_params(p)
+    return {k: named[k].detach().numpy().astype(np.float64) for k in KEYS}, rows
+
+
+@pytest.mark.parametrize('max_grad_norm', [0.05, 100.0], ids=['clipped', 'unclipped'])
+def test_adam_matches_torch(feeding, max_grad_norm):
+    """Three epochs x two minibatches from the same start: the weights read back through
+    avr_policy_get against torch float64 Adam + clip_grad_norm_ on ppo_loss_reference, under the 8 x
+    rule against the same procedure in torch CPU float32; grad_norm, approx_kl and clip_frac of every
+    minibatch against the float64 run (1e-5 absolute + 1e-4 relative: float32 evaluations whose
+    inputs, the weights, already differ by float32 rounding after the first step).  One case's norm
+    exceeds max_grad_norm at every step, the other's never does.
+    Observed on an MI355X, the tensor closest to its bound (observed / bound): clipped mu_w 7.0e-8 /
+    5.1e-7, unclipped c_b2 9.3e-8 / 3.4e-7; c_b3 2.2e-9 and 1.1e-9 / its floor 1.9e-8."""
+    import torch
+    A, md, _ = feeding
+    pol, rms = policy32(25, 64, seed=41)
+    batch = make_batch(pol, rms, 70, seed=42)
+    params = dict(PARAMS, max_grad_norm=max_grad_norm)
+    r64, rows = torch_update(pol, rms, batch, params, 3, 2, torch.float64)
+    t32, _ = torch_update(pol, rms, batch, params, 3, 2, torch.float32)
+    norms = [r['grad_norm'] for r in rows]
+    assert all(x > max_grad_norm for x in norms) if max_grad_norm < 1 else all(x < max_grad_norm for x in norms)
+    sim = make_sim(md)
+    install(sim, pol, rms)
+    pb, keep = upload(sim, batch)
+    sim.ppo_update_device(pb, sim.ppo_params(params), 3, 2)
+    d = sim.policy_get()
+    st = np.stack([stats_row(sim, i) for i in range(6)])
+    sim.close()
+    # c_b3, one number: one ulp of the weight per step (each of the 6 in-place subtractions rounds to half an ulp of
+    # |w|; the step lr m / (sqrt(v) + eps) is at most a few lr = 1e-3 in size, so its own float32 evaluation, at a
+    # relative 1e-6, stays below the other half for |w| down to lr, which the max() covers)
+    check_8x('adam[%s]' % max_grad_norm, d, t32, r64, floor=dict(c_b3=6 * U32 * max(float(np.abs(r64['c_b3']).max()), params['lr'])))
+    for i, r in enumerate(rows):
+        for col, k in ((5, 'grad_norm'), (3, 'approx_kl'), (4, 'clip_frac')):
+            print('adam stat[%d] %s: device %.9g reference %.9g' % (i, k, st[i, col], r[k]))
+            assert abs(st[i, col] - r[k]) <= 1e-5 + 1e-4 * abs(r[k]), (i, k, st[i, col], r[k])
+
+
+# ------------------------------------------------------------------ 5. determinism and composition
+def test_deterministic_and_update_equals_loop(feeding):
+    """The same update twice from the same state gives bit-identical weight blocks, and
+    avr_ppo_update_device the same bits (weights, moments, statistics) as the loop of gradient and
+    Adam calls.  8221 samples: several passes per block."""
+    import torch
+    A, md, _ = feeding
+    pol, rms = policy32(25, 64, seed=51)
+    batch = make_batch(pol, rms, 8221, seed=52)
+    perm = np.stack([np.random.default_rng(53 + e).permutation(8221) for e in range(2)]).astype(np.int32)
+    sim = make_sim(md)
+    pb, keep = upload(sim, batch)
+    dperm = torch.from_numpy(perm).cuda()
+    torch.cuda.synchronize()
+    P = sim.ppo_params(PARAMS)
+    outs = []
+    for mode in ('update', 'update', 'loop'):
+        install(sim, pol, rms)
+        if mode == 'update':
+            sim.ppo_update_device(pb, P, 2, 3, dperm.data_ptr())
+        else:
+            for ep in range(2):
+                for j in range(3):
+                    sim.ppo_grad_device(pb, P, j, 3, dperm[ep].data_ptr())
+                    sim.ppo_adam_device(P)
+        # (the last minibatch's statistics: row epoch * 3 + 2 of the update, row 2 of the single calls)
+        outs.append((block(sim, 'w'), block(sim, 'm'), block(sim, 'v'), stats_row(sim, 5 if mode == 'update' else 2)))
+    sim.close()
+    for o in outs[1:]:
+        for a, b in zip(outs[0], o):
+            assert np.array_equal(a, b)
+    assert np.all(np.isfinite(outs[0][0])) and outs[0][3][5] > 0
+
+
+# ------------------------------------------------------------------ 6. the rollout sees the update
+def test_rollout_reads_updated_weights_without_recapture(feeding, monkeypatch):
+    """16 envs, reset_pool=1: a rollout of 8 steps, an update, a second rollout.  Its logp[0] and
+    value[0] equal avr_policy_act_device on the read-back weights re-installed in a fresh handle, bit
+    for bit, and no graph is captured across the update."""
+    import torch
+    from avr import ppo
+    from avr.env import AVRTorchVecEnv
+    monkeypatch.setenv('AVR_ENV_GROUPS', '2')
+    A, md, _ = feeding
+    pol, rms = policy32(25, 64, seed=61)
+    env = AVRTorchVecEnv('FeedingJaco-v0', 16, reset_pool=1)
+    env.reset()
+    out = env.rollout_policy(pol, rms, 8)
+    adv, ret = env.compute_gae(out, 0.99, 0.95, True)
+    torch.cuda.synchronize()
+    w0 = block(env.sim, 'w')
+    c0 = env.sim.graph_captures()
+    env.ppo_update(out, adv, ret, dict(PARAMS, lr=1e-2), 2, 2, generator=torch.Generator(device='cuda').manual_seed(1))
+    t1 = env.policy_t
+    out2 = env.rollout_policy(None, None, 8)
+    torch.cuda.synchronize()
+    assert env.sim.graph_captures() == c0
+    assert not np.array_equal(block(env.sim, 'w'), w0)
+    d = env.sim.policy_get()
+    w1 = block(env.sim, 'w')
+    obs0, act0, logp0, value0 = (out2[k][0].clone() for k in ('obs', 'act', 'logp', 'value'))
+    seed = env.seed
+    env.close()
+    sim = make_sim(md, 16, seed=seed)
+    sim.policy_set(d)
+    a, lp, v = torch.zeros(16, 7, device='cuda'), torch.zeros(16, device='cuda'), torch.zeros(16, device='cuda')
+    torch.cuda.synchronize()
+    sim.policy_act_device(t1, obs0.data_ptr(), False, a.data_ptr(), lp.data_ptr(), v.data_ptr())
+    sim.sync()
+    assert np.array_equal(block(sim, 'w'), w1)                # (what avr_policy_get returned re-packs to the same block)
+    sim.close()
+    assert torch.equal(lp, logp0) and torch.equal(v, value0) and torch.equal(a, act0)
+
+
+# ------------------------------------------------------------------ 7. the trainer
+def test_trainer_end_to_end(tmp_path):
+    """ScratchItchPR2, 16 envs, 6-step rollouts, two iterate() calls; sync_module / save / load_policy
+    round-trip exactly; and on the first iteration's fixed batch the float64 reference loss at the
+    updated weights is below the loss at the initial weights (a property of small gradient steps on
+    the batch they were computed from, not a learning claim)."""
+    import copy
+    import torch
+    from avr import policy_eval as PE, ppo
+    from avr.env import AVRTorchVecEnv
+    pol, rms = policy32(30, 48, seed=71)
+    env = AVRTorchVecEnv('ScratchItchPR2-v0', 16, reset_pool=1)
+    env.reset()
+    hyper = dict(lr=1e-4, epochs=2, n_minibatch=1, update_ob_rms=False, max_grad_norm=10.0)
+    tr = ppo.PPOTrainer(env, copy.deepcopy(pol), copy.deepcopy(rms), n_steps=6, generator=torch.Generator(device='cuda').manual_seed(3), **hyper)
+    r = tr.iterate()
+    torch.cuda.synchronize()
+    batch = {k: v.detach().cpu().clone() for k, v in ppo.flatten_rollout(tr.last['out'], tr.last['adv'], tr.last['ret']).items()}
+    assert r['stats'].shape == (2, 6) and bool(torch.isfinite(r['stats']).all())
+    assert float(batch['adv'].std()) > 1e-3                                  # non-degenerate advantages
+    after1, _ = tr.sync_module()
+    after1 = copy.deepcopy(after1)
+    P = dict(ppo.DEFAULTS, **hyper)
+    b64 = {k: v.double() for k, v in batch.items()}
+    with torch.no_grad():
+        l0, _ = ppo.ppo_loss_reference(copy.deepcopy(pol).double(), rms, b64, None, P)
+        l1, _ = ppo.ppo_loss_reference(after1.double(), rms, b64, None, P)
+    print('trainer: float64 loss on the first batch %.9g -> %.9g' % (float(l0), float(l1)))
+    assert float(l1) < float(l0)
+    # with the running statistics on: the block's ob_rms rows follow the device-side update
+    tr.hyper.update(update_ob_rms=True, n_minibatch=3)
+    r2 = tr.iterate()
+    assert bool(torch.isfinite(r2['stats']).all()) and tr.iterations == 2
+    path = str(tmp_path / 'ppo.pt')
+    tr.save(path)
+    d = env.sim.policy_get()
+    env.close()
+    obs_all = tr.last['out']['obs'][:6].reshape(-1, 30).double().cpu().numpy()
+    want = PE.RunningMeanStd((30,), rms.mean, rms.var, rms.count)
+    want.update(obs_all)
+    assert np.allclose(d['ob_mean'], want.mean, rtol=1e-6, atol=1e-7) and np.allclose(d['ob_var'], want.var, rtol=1e-5, atol=1e-7)
+    pol2, rms2 = PE.load_policy(path)
+    for k, p in ppo.module_params(pol2).items():
+        assert np.array_equal(p.detach().numpy().reshape(d[k].shape), d[k]), k
+    assert np.array_equal(rms2.mean, d['ob_mean'].astype(np.float64)) and np.array_equal(rms2.var, d['ob_var'].astype(np.float64))
+    for a, b in zip(tr.actor_critic.state_dict().values(), pol2.state_dict().values()):
+        assert torch.equal(a.cpu(), b)
+    r = PE.evaluate('ScratchItchPR2-v0', pol2, rms2, n_envs=16, steps=4, deterministic=True, fused=True)      # the checkpoint runs fused
+    assert r['fused'] is True and r['returns'].shape == (16,) and np.all(np.isfinite(r['returns']))
+
+
+# ------------------------------------------------------------------ 8. error paths
+def test_errors(feeding):
+    import torch
+    from avr import _abi as ABI, _lib, reset_dressing as RD
+    A, md, _ = feeding
+    pol, rms = policy32(25, 64, seed=81)
+    batch = make_batch(pol, rms, 16, seed=82)
+    sim = make_sim(md)
+    pb, keep = upload(sim, batch)
+    P = sim.ppo_params(PARAMS)
+    with pytest.raises(RuntimeError, match='avr_policy_set first'):
+        sim.ppo_reset()
+    with pytest.raises(RuntimeError, match='avr_policy_set first'):
+        sim.ppo_grad_device(pb, P, 0, 1)
+    with pytest.raises(RuntimeError, match='avr_policy_set first'):
+        sim.policy_get()
+    from avr import policy_eval as PE
+    d = PE.policy_desc(pol, rms, 25, 7)
+    sim.policy_set(d)
+    for call in (lambda: sim.ppo_grad_device(pb, P, 0, 1), lambda: sim.ppo_adam_device(P), lambda: sim.ppo_update_device(pb, P, 1, 1), sim.ppo_buffers):
+        with pytest.raises(RuntimeError, match='avr_ppo_reset first'):
+            call()
+    sim.ppo_reset()
+    lib, h = sim.lib, sim.h
+    assert lib.avr_ppo_grad_device(h, None, C.byref(P), 0, 1, None) == -1 and b'batch is NULL' in lib.avr_last_error(h)
+    assert lib.avr_ppo_grad_device(h, C.byref(pb), None, 0, 1, None) == -1 and b'params is NULL' in lib.avr_last_error(h)
+    assert lib.avr_ppo_adam_device(h, None) == -1
+    assert lib.avr_policy_get(h, None) == -1
+    assert lib.avr_gae_device(h, 2, 0.99, 0.95, 0, None, None, None, None, None) == -1 and b'must be given' in lib.avr_last_error(h)
+    for M in (0, 17):
+        with pytest.raises(RuntimeError, match='n_minibatch'):
+            sim.ppo_grad_device(pb, P, 0, M)
+    with pytest.raises(RuntimeError, match='minibatch 2 outside'):
+        sim.ppo_grad_device(pb, P, 2, 2)
+    with pytest.raises(RuntimeError, match='before minibatch 0'):          # (no advantage statistics of this batch yet)
+        sim.ppo_grad_device(pb, P, 1, 2)
+    sim.ppo_grad_device(pb, sim.ppo_params(dict(PARAMS, norm_adv=False)), 1, 2)
+    sim.ppo_grad_device(pb, P, 0, 2)
+    sim.ppo_grad_device(pb, P, 1, 2)
+    sim.ppo_reset()                                                        # (forgets them)
+    with pytest.raises(RuntimeError, match='before minibatch 0'):
+        sim.ppo_grad_device(pb, P, 1, 2)
+    with pytest.raises(RuntimeError, match='epochs 0'):
+        sim.ppo_update_device(pb, P, 0, 1)
+    noobs = sim.ppo_batch(1, 16, **{k: keep[k].data_ptr() for k in keep if k != 'obs'})
+    with pytest.raises(RuntimeError, match='must be given'):
+        sim.ppo_grad_device(noobs, P, 0, 1)
+    with pytest.raises(RuntimeError, match='n 0'):
+        sim.ppo_grad_device(sim.ppo_batch(0, 16, **{k: keep[k].data_ptr() for k in keep}), P, 0, 1)
+    # no critic installed while vf_coef != 0; fine with vf_coef = 0
+    sim.policy_set(dict(d, c_w1=None, c_b1=None, c_w2=None, c_b2=None, c_w3=None, c_b3=None))
+    with pytest.raises(RuntimeError, match='without a critic'):
+        sim.ppo_grad_device(pb, P, 0, 1)
+    sim.ppo_grad_device(pb, sim.ppo_params(dict(PARAMS, vf_coef=0.0)), 0, 1)
+    from avr import ppo
+    g = block(sim, 'g')
+    assert np.all(g[~ppo.block_live_mask(25, 7, 64, has_critic=False)] == 0) and np.any(g != 0)
+    # the ob_rms rows from device arrays; an error without ob_rms
+    m = torch.arange(25, device='cuda', dtype=torch.float32)
+    v = torch.full((25,), 3.0, device='cuda')
+    torch.cuda.synchronize()
+    sim.policy_obs_norm_device(m.data_ptr(), v.data_ptr())
+    w = block(sim, 'w')
+    assert np.array_equal(w[ppo.PW_MEAN:ppo.PW_MEAN + 25], np.arange(25, dtype=np.float32))
+    assert np.all(w[ppo.PW_SD:ppo.PW_SD + 25] == np.float32(np.sqrt(np.float64(3.0) + np.float64(np.float32(1e-8)))))
+    # a variance of 0 reads back as a non-negative variance that re-packs to the same block
+    v[3] = 0.0
+    torch.cuda.synchronize()
+    sim.policy_obs_norm_device(m.data_ptr(), v.data_ptr())
+    w, back = block(sim, 'w'), sim.policy_get()
+    assert np.all(back['ob_var'] >= 0) and back['ob_var'][3] < 1e-12 and abs(back['ob_var'][0] - 3.0) < 1e-6
+    sim.policy_set(back)
+    assert np.array_equal(block(sim, 'w'), w)
+    sim.policy_set(PE.policy_desc(pol, None, 25, 7))
+    with pytest.raises(RuntimeError, match='no ob_rms'):
+        sim.policy_obs_norm_device(m.data_ptr(), v.data_ptr())
+    sim.close()
+    dr = make_sim(ABI.ModelDesc(RD.dressing_scene()), 2)
+    for rc in (dr.lib.avr_ppo_reset(dr.h), dr.lib.avr_gae_device(dr.h, 1, 0.99, 0.95, 0, None, None, None, None, None),
+               dr.lib.avr_ppo_grad_device(dr.h, None, None, 0, 1, None), dr.lib.avr_ppo_adam_device(dr.h, None),
+               dr.lib.avr_ppo_update_device(dr.h, None, None, 1, 1, None), dr.lib.avr_ppo_buffers(dr.h, None, None, None, None),
+               dr.lib.avr_policy_get(dr.h, None), dr.lib.avr_policy_obs_norm_device(dr.h, None, None)):
+        assert rc == -1 and b'not built for DressingJaco' in dr.lib.avr_last_error(dr.h)
+    dr.close()
