@@ -26,10 +26,18 @@ EXPORTS = [
     'avr_human_variants_set', 'avr_human_variants', 'avr_human_variant_info', 'avr_narrowphase_query_slots',
     'avr_gae_device', 'avr_ppo_reset', 'avr_ppo_grad_device', 'avr_ppo_adam_device', 'avr_ppo_update_device', 'avr_ppo_buffers',
     'avr_ppo_words', 'avr_policy_block', 'avr_policy_get', 'avr_policy_obs_norm_device',
+    'avr_reward_norm_device', 'avr_episode_stats_device', 'avr_train_stats_reset', 'avr_train_stats_buffers',
 ]
 PPO_STAT_WORDS, PPO_STATS_ROWS = 8, 256      # include/avr.h AVR_PPO_STAT_WORDS, AVR_PPO_STATS_ROWS
 PPO_STATS = ('policy_loss', 'value_loss', 'entropy', 'approx_kl', 'clip_frac', 'grad_norm')   # a statistics row's first words
-MAX_HUMAN_VARIANTS = 64      # include/avr.h AVR_MAX_HUMAN_VARIANTS
+# include/avr.h AVR_EPSTAT_WORDS: the columns of avr_episode_stats_device's aggregate row (float64)
+EPISODE_STATS = ('episodes', 'ret_sum', 'ret_sumsq', 'ret_min', 'ret_max', 'len_sum', 'success_sum', 'force_mean_sum', 'steps', 'rew_sum')
+EPSTAT_WORDS = len(EPISODE_STATS)
+# include/avr.h AVR_EPENV_*: the per-env episode rows (4-byte words) and each row's dtype
+EPISODE_ENV_ROWS = (('ep_ret', '<f4'), ('ep_len', '<i4'), ('ep_force', '<f4'), ('last_ret', '<f4'), ('last_len', '<i4'), ('last_success', '<f4'),
+                    ('n_finished', '<i4'))
+TS_RED_THREADS = 256         # csrc/avr_trainstats.hip: threads of a reduction block (a thread folds envs t, t + 256, ...)
+MAX_HUMAN_VARIANTS = 64     # include/avr.h AVR_MAX_HUMAN_VARIANTS
 FLAGS_FAULT_MASK = 0x1f      # include/avr.h AVR_FLAGS_FAULT_MASK: bits 0-4; bit 5 (EPA budget) is informational
 
 
@@ -132,6 +140,11 @@ def load(path=LIB_PATH):
         lib.avr_policy_block.restype = vp
         lib.avr_policy_get.argtypes = [vp, C.POINTER(avr_policy_out)]
         lib.avr_policy_obs_norm_device.argtypes = [vp, vp, vp]
+    if hasattr(lib, 'avr_train_stats_reset'):       # (absent in experiment builds of older trees)
+        lib.avr_reward_norm_device.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, vp, vp, vp]
+        lib.avr_episode_stats_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
+        lib.avr_train_stats_reset.argtypes = [vp]
+        lib.avr_train_stats_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.avr_sync.argtypes = [vp]
     lib.avr_stream.argtypes = [vp]
     lib.avr_stream.restype = vp
@@ -488,6 +501,30 @@ class Sim:
     def policy_obs_norm_device(self, d_mean, d_var):
         """Rewrite the weight block's ob_rms rows from device float32 arrays [obs_dim] in stream order."""
         self._chk(self.lib.avr_policy_obs_norm_device(self.h, d_mean, d_var))
+
+    # ---- reward normalisation and episode statistics (include/avr.h avr_reward_norm_device, avr_episode_stats_device)
+    def reward_norm_device(self, n, gamma, clip_rew, eps, update, d_rew, d_done, d_rew_out):
+        """VecNormalize's reward path over a rollout's stacked [n, n_envs] device arrays: d_rew_out (may be
+        d_rew) = clamp(rew / sqrt(var + eps), +-clip_rew) with the running variance of the discounted return;
+        update False: eval mode, the carried return and statistics stay untouched."""
+        self._chk(self.lib.avr_reward_norm_device(self.h, int(n), float(gamma), float(clip_rew), float(eps), int(bool(update)), d_rew, d_done, d_rew_out))
+
+    def episode_stats_device(self, n, d_rew, d_done, d_info, d_row=None):
+        """Advance the per-env episode accumulators over a rollout's stacked device arrays; d_row (device
+        float64 [EPSTAT_WORDS], columns EPISODE_STATS; None: only the handle's own row) receives the
+        aggregate over the episodes closed in this call."""
+        self._chk(self.lib.avr_episode_stats_device(self.h, int(n), d_rew, d_done, d_info, d_row))
+
+    def train_stats_reset(self):
+        """Allocate / zero the carried rows of the two calls above; the return's moments become (0, 1, 1e-4)."""
+        self._chk(self.lib.avr_train_stats_reset(self.h))
+
+    def train_stats_buffers(self):
+        """Device pointers (R [n_envs] float64, (mean, var, count) [3] float64, the per-env episode rows
+        [len(EPISODE_ENV_ROWS), n_envs] of 4-byte words, the last aggregate row [EPSTAT_WORDS] float64)."""
+        p = [C.c_void_p() for _ in range(4)]
+        self._chk(self.lib.avr_train_stats_buffers(self.h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
 
     # ---- human height variants (include/avr.h avr_human_variants_set)
     def human_variants_set(self, records):

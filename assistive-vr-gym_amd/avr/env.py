@@ -783,6 +783,50 @@ class AVRTorchVecEnv(AVRVecEnv):
         rows = min(int(epochs) * int(n_minibatch), _lib.PPO_STATS_ROWS)
         return self._ppo_stats[:rows, :len(_lib.PPO_STATS)].clone()
 
+    # ------------------------------------------------------------------ reward normalisation and episode statistics
+    def normalize_rewards(self, out, gamma, clip_rew=10.0, eps=1e-8, update=True):
+        """VecNormalize's reward half on a rollout_policy result, on the device in stream order
+        (include/avr.h avr_reward_norm_device): out['rew'] / sqrt(var + eps) clipped to +-clip_rew, var the
+        running variance of the discounted return, which the handle carries across rollouts (reset by
+        train_stats_reset).  update False: eval mode, the carried state is only read.  out['rew'] itself
+        is left as it is; the returned [n, E] tensor is the env's own, one per rollout length."""
+        torch = self.torch
+        n, E = out['rew'].shape
+        B = self._roll.setdefault(('rew_norm', n), {})
+        if not B:
+            B['rew'] = torch.zeros(n, E, device=self.dev)
+        self.ext.wait_stream(torch.cuda.current_stream(self.dev))
+        self.sim.reward_norm_device(n, gamma, clip_rew, eps, update, out['rew'].data_ptr(), out['done'].data_ptr(), B['rew'].data_ptr())
+        torch.cuda.current_stream(self.dev).wait_stream(self.ext)
+        return B['rew']
+
+    def _train_stats_row(self):
+        from . import _lib
+        if getattr(self, '_ep_row', None) is None:
+            self._ep_row = self._wrap(self.sim.train_stats_buffers()[3], (_lib.EPSTAT_WORDS,), '<f8')
+        return self._ep_row
+
+    def episode_stats(self, out):
+        """Advance the handle's per-env episode accumulators over a rollout_policy result (its raw rew, done
+        and info) in stream order and return the aggregate over the episodes that ended in it: a cloned
+        device float64 row with the columns _lib.EPISODE_STATS (include/avr.h avr_episode_stats_device;
+        PPOTrainer.episode_summary turns it into means).  Nothing is synchronised."""
+        torch = self.torch
+        n = out['rew'].shape[0]
+        row = self._train_stats_row()
+        self.ext.wait_stream(torch.cuda.current_stream(self.dev))
+        self.sim.episode_stats_device(n, out['rew'].data_ptr(), out['done'].data_ptr(), out['info'].data_ptr())
+        torch.cuda.current_stream(self.dev).wait_stream(self.ext)
+        return row.clone()
+
+    def train_stats_reset(self):
+        """Zero the state normalize_rewards and episode_stats carry across rollouts: the discounted returns,
+        their running moments (back to mean 0, var 1, count 1e-4) and the episode accumulators."""
+        torch = self.torch
+        self.ext.wait_stream(torch.cuda.current_stream(self.dev))
+        self.sim.train_stats_reset()
+        torch.cuda.current_stream(self.dev).wait_stream(self.ext)
+
     def close(self):
         self.torch.cuda.synchronize(self.dev)
         super().close()

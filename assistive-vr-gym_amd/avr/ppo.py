@@ -6,7 +6,9 @@ harness's ActorCritic (avr/policy_eval.py); the reference ships neither that lib
 trainer or settings, so the hyper-parameter defaults below are this facade's own choice, not the
 reference's.  gae_reference and ppo_loss_reference are the same formulas as the kernels in numpy
 and torch at any dtype: the tests use them as the reference, and they can be read next to the
-kernels.
+kernels.  reward_norm_reference and episode_stats_reference do the same for the reward half of
+VecNormalize and the episode statistics (csrc/avr_trainstats.hip, include/avr.h
+avr_reward_norm_device / avr_episode_stats_device).
 """
 import numpy as np
 import torch
@@ -24,7 +26,10 @@ DEFAULTS = dict(
     norm_adv=True, clip_value=True,
     epochs=4, n_minibatch=8,                        # passes over the batch, minibatches per pass
     update_ob_rms=True,                             # keep VecNormalize's running observation statistics
+    norm_reward=False, clip_reward=10.0,            # VecNormalize's reward half: rew / sqrt(var(discounted return) + 1e-8), clipped
+    episode_stats=True,                             # reduce the episodes that ended in the rollout (episode_summary)
 )
+RET_EPS = 1e-8                                      # VecNormalize's epsilon
 
 # the device weight block (csrc/avr_policy.hip PW_* / PN_*), in floats
 POL_H = 64
@@ -115,6 +120,95 @@ def gae_reference(rew, done, value, term_value=None, gamma=0.99, lam=0.95, boots
     return adv, ret
 
 
+def train_stats_state(E):
+    """The state avr_train_stats_reset leaves in a handle of E envs, as the dict the two mirrors below
+    carry from call to call: the discounted returns R and their running moments (ret_rms), the running
+    episodes' accumulators and each env's last finished episode."""
+    z = lambda dt: np.zeros(E, dt)
+    return dict(R=z(np.float64), mean=0.0, var=1.0, count=1e-4,
+                ep_ret=z(np.float32), ep_len=z(np.int32), ep_force=z(np.float32),
+                last_ret=z(np.float32), last_len=z(np.int32), last_success=z(np.float32), n_finished=z(np.int32))
+
+
+def reward_norm_reference(rew, done, state, gamma=0.99, clip_rew=10.0, eps=RET_EPS, update=True):
+    """VecNormalize's reward path over stacked [n, E] arrays -> rew_out [n, E] float32, in float64 in the
+    device call's phases (csrc/avr_trainstats.hip, include/avr.h avr_reward_norm_device); `state`
+    (train_stats_state) is advanced in place unless update is False (eval mode: only the scaling).
+      1. per env, k ascending:  R = R * gamma + rew[k];  Rk[k] = R;  R = 0 at done[k]
+      2. per step:              bm[k] = mean_e Rk[k], bv[k] = mean_e (Rk[k] - bm[k])^2
+      3. k ascending:           RunningMeanStd.update's merge of (bm[k], bv[k], E) into (mean, var, count);
+                                var_k[k] = var after it
+      4. elementwise:           clip(rew[k] / sqrt(var_k[k] + eps), -clip_rew, clip_rew) as float32
+    A step's rewards are scaled with the statistics after that step's update, as baselines does."""
+    rew = np.asarray(rew, np.float32).astype(np.float64)
+    done = np.asarray(done).astype(bool)
+    n, E = rew.shape
+    if update:
+        R, Rk = state['R'].copy(), np.zeros((n, E))
+        for k in range(n):
+            R = R * gamma + rew[k]
+            Rk[k] = R
+            R = np.where(done[k], 0.0, R)
+        bm = Rk.mean(1)
+        bv = ((Rk - bm[:, None]) ** 2).mean(1)
+        mean, var, count, bc = float(state['mean']), float(state['var']), float(state['count']), float(E)
+        var_k = np.zeros(n)
+        for k in range(n):
+            d = float(bm[k]) - mean
+            tot = count + bc
+            new_mean = mean + d * bc / tot
+            var = (var * count + float(bv[k]) * bc + d * d * count * bc / tot) / tot
+            mean, count = new_mean, tot
+            var_k[k] = var
+        state.update(R=R, mean=mean, var=var, count=count)
+    else:
+        var_k = np.full(n, float(state['var']))
+    return np.clip(rew / np.sqrt(var_k + eps)[:, None], -clip_rew, clip_rew).astype(np.float32)
+
+
+def episode_stats_reference(rew, done, info, state):
+    """The aggregate row (float64 [len(_lib.EPISODE_STATS)]) of the episodes that end inside stacked
+    rew / done [n, E], info [n, E, 2] = {total_force_on_human, task_success}, in the device call's
+    phases (include/avr.h avr_episode_stats_device); `state` (train_stats_state) is advanced in place.
+      1. per env, k ascending: ep_ret += rew[k] and ep_force += info[k][0] in float32, ep_len += 1; at
+         done[k] the episode closes with (ep_ret, ep_len, info[k][1], ep_force / ep_len), becomes the env's
+         last finished one and adds to the env's share of every column in float64; the accumulators restart
+      2. per column: the envs' shares summed (ret_min / ret_max: min / max)
+    With no episode closed ret_min = +inf and ret_max = -inf."""
+    rew, info = np.asarray(rew, np.float32), np.asarray(info, np.float32)
+    done = np.asarray(done).astype(bool)
+    n, E = rew.shape
+    S = state
+    names = ('episodes', 'ret_sum', 'ret_sumsq', 'ret_min', 'ret_max', 'len_sum', 'success_sum', 'force_mean_sum', 'steps', 'rew_sum')
+    P = {c: np.zeros(E) for c in names}
+    P['ret_min'][:], P['ret_max'][:] = np.inf, -np.inf
+    for k in range(n):
+        S['ep_ret'] = S['ep_ret'] + rew[k]
+        S['ep_force'] = S['ep_force'] + info[k, :, 0]
+        S['ep_len'] = S['ep_len'] + np.int32(1)
+        P['rew_sum'] += rew[k].astype(np.float64)
+        d = done[k]
+        if d.any():
+            ret, ln = S['ep_ret'][d].astype(np.float64), S['ep_len'][d].astype(np.float64)
+            P['episodes'][d] += 1.0
+            P['ret_sum'][d] += ret
+            P['ret_sumsq'][d] += ret * ret
+            P['ret_min'][d] = np.minimum(P['ret_min'][d], ret)
+            P['ret_max'][d] = np.maximum(P['ret_max'][d], ret)
+            P['len_sum'][d] += ln
+            P['success_sum'][d] += info[k, d, 1].astype(np.float64)
+            P['force_mean_sum'][d] += S['ep_force'][d].astype(np.float64) / ln
+            S['last_ret'] = np.where(d, S['ep_ret'], S['last_ret'])
+            S['last_len'] = np.where(d, S['ep_len'], S['last_len'])
+            S['last_success'] = np.where(d, info[k, :, 1], S['last_success'])
+            S['n_finished'] = S['n_finished'] + d.astype(np.int32)
+            S['ep_ret'] = np.where(d, np.float32(0), S['ep_ret'])
+            S['ep_force'] = np.where(d, np.float32(0), S['ep_force'])
+            S['ep_len'] = np.where(d, np.int32(0), S['ep_len'])
+    P['steps'][:] = float(n)
+    return np.array([P[c].min() if c == 'ret_min' else P[c].max() if c == 'ret_max' else P[c].sum() for c in names])
+
+
 def ppo_loss_reference(actor_critic, ob_rms, batch, idx, params):
     """The loss of one minibatch and its statistics, in the dtype of the module's parameters.
 
@@ -182,9 +276,19 @@ class PPOTrainer:
     fresh RunningMeanStd); n_steps: steps per rollout.  hyper: any of DEFAULTS' keys --
       gamma 0.99, lam 0.95, bootstrap True (a TimeLimit done bootstraps from V(terminal observation)),
       clip 0.2, vf_coef 0.5, ent_coef 0.0, max_grad_norm 0.5, lr 3e-4, beta1 0.9, beta2 0.999, eps 1e-5,
-      norm_adv True, clip_value True, epochs 4, n_minibatch 8, update_ob_rms True.
+      norm_adv True, clip_value True, epochs 4, n_minibatch 8, update_ob_rms True,
+      norm_reward False, clip_reward 10.0, episode_stats True.
     These defaults are this facade's own choice: the reference ships neither its trainer nor its
-    settings.  generator: a torch.Generator on the env's device for the minibatch permutations."""
+    settings.  generator: a torch.Generator on the env's device for the minibatch permutations.
+
+    norm_reward: the reward half of baselines' VecNormalize (the a2c_ppo_acktr pipeline's wrapper): the
+    advantages are estimated from rew / sqrt(var + 1e-8) clipped to +-clip_reward, var the running
+    variance of the discounted return (gamma), carried across iterations on the device
+    (env.normalize_rewards).  The critic then learns returns of normalised rewards: `value` and `ret`
+    are in normalised-reward units, not the task's.  save() stores the policy and ob_rms only, as
+    before; the return statistics stay in the handle (_lib.Sim.train_stats_buffers).
+    episode_stats: every iteration reduces the episodes that ended inside its rollout, from the raw
+    rewards (env.episode_stats); episode_summary reads such a row on the host."""
 
     def __init__(self, env, actor_critic, ob_rms=None, n_steps=128, generator=None, **hyper):
         bad = set(hyper) - set(DEFAULTS)
@@ -199,6 +303,7 @@ class PPOTrainer:
         self.ob_rms = ob_rms if ob_rms is not None else PE.RunningMeanStd((env.L.OBS_DIM,))
         env.set_policy(actor_critic, self.ob_rms)
         env.ppo_reset()                             # (a new network: Adam starts from zero moments)
+        env.train_stats_reset()                     # (a new run: no return statistics, no episode under way)
         dev = env.dev
         # VecNormalize's running statistics on the device (float64; the block receives float32 copies)
         self._mean = torch.as_tensor(np.asarray(self.ob_rms.mean, np.float64), device=dev)
@@ -225,19 +330,47 @@ class PPOTrainer:
         torch_.cuda.current_stream(env.dev).wait_stream(env.ext)
 
     def iterate(self):
-        """One PPO iteration: rollout, (optional) ob_rms update, advantage estimation, update.  Returns
-        device tensors: the update's statistics rows [epochs * n_minibatch, 6] under 'stats' (columns
-        _lib.PPO_STATS) and the rollout's mean reward under 'mean_reward'; nothing is synchronised."""
+        """One PPO iteration: rollout, (optional) ob_rms update, episode statistics, (optional) reward
+        normalisation, advantage estimation, update.  Returns device tensors: the update's statistics
+        rows [epochs * n_minibatch, 6] under 'stats' (columns _lib.PPO_STATS), the rollout's mean raw
+        reward under 'mean_reward' and, with episode_stats, the aggregate row of the episodes that ended
+        in the rollout under 'episodes' (float64, columns _lib.EPISODE_STATS; episode_summary reads it);
+        nothing is synchronised."""
         h, env = self.hyper, self.env
         out = env.rollout_policy(None, None, self.n_steps)
         if h['update_ob_rms']:
             # (the batch keeps the raw observations: the update normalises them with the new statistics)
             self._update_ob_rms(out['obs'][:out['n']])
-        adv, ret = env.compute_gae(out, h['gamma'], h['lam'], h['bootstrap'])
+        res = {}
+        if h['episode_stats']:
+            res['episodes'] = env.episode_stats(out)                # (the raw rewards, whatever the update trains on)
+        rew_norm = None
+        if h['norm_reward']:
+            rew_norm = env.normalize_rewards(out, h['gamma'], h['clip_reward'], RET_EPS, update=True)
+            adv, ret = env.compute_gae(dict(out, rew=rew_norm), h['gamma'], h['lam'], h['bootstrap'])
+        else:
+            adv, ret = env.compute_gae(out, h['gamma'], h['lam'], h['bootstrap'])
         stats = env.ppo_update(out, adv, ret, h, h['epochs'], h['n_minibatch'], generator=self.generator)
         self.iterations += 1
-        self.last = dict(out=out, adv=adv, ret=ret)
-        return dict(stats=stats, mean_reward=out['rew'].mean())
+        self.last = dict(out=out, adv=adv, ret=ret, rew_norm=rew_norm)
+        return dict(res, stats=stats, mean_reward=out['rew'].mean())
+
+    @staticmethod
+    def episode_summary(row):
+        """An 'episodes' row of iterate() (or the sum of several: every column but ret_min / ret_max adds)
+        as Python numbers -- the one blocking helper: it copies the row to the host.  Keys: episodes,
+        return_mean, return_std (population), return_min, return_max, length_mean, success_rate,
+        force_mean (the mean over episodes of the episode's mean total_force_on_human); all but episodes
+        are None when no episode ended."""
+        from . import _lib
+        r = dict(zip(_lib.EPISODE_STATS, (float(x) for x in torch.as_tensor(row).detach().cpu().tolist())))
+        m = int(r['episodes'])
+        keys = ('return_mean', 'return_std', 'return_min', 'return_max', 'length_mean', 'success_rate', 'force_mean')
+        if m == 0:
+            return dict(dict.fromkeys(keys), episodes=0)
+        mean = r['ret_sum'] / m
+        return dict(episodes=m, return_mean=mean, return_std=max(r['ret_sumsq'] / m - mean * mean, 0.0) ** 0.5, return_min=r['ret_min'],
+                    return_max=r['ret_max'], length_mean=r['len_sum'] / m, success_rate=r['success_sum'] / m, force_mean=r['force_mean_sum'] / m)
 
     def sync_module(self):
         """Copy the device weights and observation statistics back into the torch module and ob_rms

@@ -60,6 +60,12 @@
     void *avr_policy_block(avr_sim *s);                                                                            \
     int avr_policy_get(avr_sim *s, avr_policy_out *out);                                                           \
     int avr_policy_obs_norm_device(avr_sim *s, const float *d_mean, const float *d_var);                           \
+    int avr_reward_norm_device(avr_sim *s, int32_t n, double gamma, double clip_rew, double eps, int32_t update,    \
+                               const float *d_rew, const uint8_t *d_done, float *d_rew_out);                       \
+    int avr_episode_stats_device(avr_sim *s, int32_t n, const float *d_rew, const uint8_t *d_done,                 \
+                                 const float *d_info, double *d_row);                                              \
+    int avr_train_stats_reset(avr_sim *s);                                                                         \
+    int avr_train_stats_buffers(avr_sim *s, double **d_R, double **d_rms, void **d_env, double **d_row);           \
     int avr_human_variants_set(avr_sim *s, int32_t n_var, const avr_human_variant *v);                             \
     int32_t avr_human_variants(avr_sim *s);                                                                        \
     int avr_human_variant_info(avr_sim *s, int32_t v, int32_t *gender, float *height);                             \
@@ -254,6 +260,14 @@ void *avr_policy_block(avr_sim *s) {
 }
 int avr_policy_get(avr_sim *s, avr_policy_out *o) { DISPATCH(s, avr_policy_get(h, o)); }
 int avr_policy_obs_norm_device(avr_sim *s, const float *m, const float *v) { DISPATCH(s, avr_policy_obs_norm_device(h, m, v)); }
+int avr_reward_norm_device(avr_sim *s, int32_t n, double gamma, double clip, double eps, int32_t update, const float *r, const uint8_t *d, float *o) {
+    DISPATCH(s, avr_reward_norm_device(h, n, gamma, clip, eps, update, r, d, o));
+}
+int avr_episode_stats_device(avr_sim *s, int32_t n, const float *r, const uint8_t *d, const float *i, double *row) {
+    DISPATCH(s, avr_episode_stats_device(h, n, r, d, i, row));
+}
+int avr_train_stats_reset(avr_sim *s) { DISPATCH(s, avr_train_stats_reset(h)); }
+int avr_train_stats_buffers(avr_sim *s, double **R, double **rms, void **env, double **row) { DISPATCH(s, avr_train_stats_buffers(h, R, rms, env, row)); }
 int avr_substep(avr_sim *s, float dt) { DISPATCH(s, avr_substep(h, dt)); }
 int avr_sync(avr_sim *s) { DISPATCH(s, avr_sync(h)); }
 int avr_kernel_info(avr_sim *s, int32_t *o) { DISPATCH(s, avr_kernel_info(h, o)); }

@@ -85,6 +85,14 @@ struct avr_sim {
     int ppo_row;                           // the statistics row the last gradient call wrote
     const float *ppo_adv;                  // the batch (adv pointer, sample count) whose advantage mean / std the
     long long ppo_adv_n;                   //   device holds (NULL: none)
+    // reward normalisation and episode statistics (avr_train_stats_reset, avr_trainstats.hip): one block of
+    // the discounted-return row R[n_envs], the running moments (mean, var, count), the aggregate row, the
+    // per-env shares of an aggregate [AVR_EPSTAT_WORDS][n_envs] and the per-env episode rows
+    // [AVR_EPENV_ROWS][n_envs]; and the reward normalisation's scratch, which grows with the rollout length
+    double *d_ts_R, *d_ts_rms, *d_ts_row, *d_ts_part;
+    float *d_ts_env;
+    double *d_ts_scr;
+    size_t ts_cap;
     // device-side episode rollover (avr_reset_pool_set, avr_rollover_*; avr_rollover.hip): the pool
     // block (header, pool_cap state rows, pool_cap observation rows), whose address the rollout
     // graphs of the rollover mode hold, and the per-env terminal observation / value / episode
@@ -695,6 +703,7 @@ int avr_destroy(avr_sim *s) {
     if (s->d_query) (void)hipFree(s->d_query);
     if (s->d_ik) (void)hipFree(s->d_ik);
     if (s->d_bs) (void)hipFree(s->d_bs);
+    if (s->d_ts_scr) (void)hipFree(s->d_ts_scr);
     for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
     for (int i = 0; i < s->ngroups; i++) {
         if (s->gstream[i]) (void)hipStreamDestroy(s->gstream[i]);
@@ -1494,6 +1503,75 @@ int avr_policy_obs_norm_device(avr_sim *s, const float *d_mean, const float *d_v
     if (!s->pol_norm) return fail(s, -1, "avr_policy_obs_norm_device: the installed policy has no ob_rms");
     if (!d_mean || !d_var) return fail(s, -1, "avr_policy_obs_norm_device: d_mean and d_var must be given");
     HIPCHK(s, avr_launch_obs_norm(s->d_pol, d_mean, d_var, s->pol_eps, s->stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------ reward normalisation and episode statistics
+// allocate (first call) the carried rows; reset: zero them and set the moments / the aggregate row
+static int train_stats_state(avr_sim *s, bool reset) {
+    const size_t E = (size_t)s->cfg.n_envs;
+    const size_t hdr = 4 + ((AVR_EPSTAT_WORDS + 3) & ~3);                    // the moments (padded to 4), the aggregate row
+    const size_t dw = E + hdr + AVR_EPSTAT_WORDS * E, fw = AVR_EPENV_ROWS * E;
+    if (!s->d_ts_R) {
+        // one block: the doubles first (alignment), then the 4-byte episode rows
+        double *blk = nullptr;
+        HIPCHK(s, hipMalloc(&blk, dw * sizeof(double) + fw * sizeof(float)));
+        s->allocs.push_back(blk);
+        s->d_ts_rms = blk + E; s->d_ts_row = s->d_ts_rms + 4; s->d_ts_part = blk + E + hdr;
+        s->d_ts_env = (float *)(blk + dw);
+        s->d_ts_R = blk;
+        reset = true;
+    }
+    if (reset) {
+        HIPCHK(s, hipMemsetAsync(s->d_ts_R, 0, dw * sizeof(double) + fw * sizeof(float), s->stream));
+        HIPCHK(s, avr_launch_train_stats_init(s->d_ts_rms, s->d_ts_row, s->stream));
+    }
+    return 0;
+}
+
+int avr_train_stats_reset(avr_sim *s) {
+    CHECK_SIM(s);
+    return train_stats_state(s, true);
+}
+
+int avr_reward_norm_device(avr_sim *s, int32_t n, double gamma, double clip_rew, double eps, int32_t update, const float *d_rew,
+                           const uint8_t *d_done, float *d_rew_out) {
+    CHECK_SIM(s);
+    if (n < 1) return fail(s, -1, "avr_reward_norm_device: n %d < 1", (int)n);
+    if (!d_rew || !d_done || !d_rew_out) return fail(s, -1, "avr_reward_norm_device: d_rew, d_done and d_rew_out must be given");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(s, -1, "avr_reward_norm_device: gamma %g outside [0, 1]", gamma);
+    if (!(eps > 0.0)) return fail(s, -1, "avr_reward_norm_device: eps %g must be > 0", eps);
+    if (!(clip_rew >= 0.0)) return fail(s, -1, "avr_reward_norm_device: clip_rew %g < 0", clip_rew);
+    if (int r = train_stats_state(s, false)) return r;
+    const size_t E = (size_t)s->cfg.n_envs, need = (size_t)n * E + 3 * (size_t)n;
+    if (update && need > s->ts_cap) {
+        if (s->d_ts_scr) HIPCHK(s, hipFree(s->d_ts_scr));
+        s->d_ts_scr = nullptr;
+        s->ts_cap = 0;
+        HIPCHK(s, hipMalloc(&s->d_ts_scr, need * sizeof(double)));
+        s->ts_cap = need;
+    }
+    HIPCHK(s, avr_launch_reward_norm(d_rew, d_done, n, (int)E, gamma, clip_rew, eps, update != 0, s->d_ts_R, s->d_ts_rms, s->d_ts_scr, d_rew_out,
+                                     s->stream));
+    return 0;
+}
+
+int avr_episode_stats_device(avr_sim *s, int32_t n, const float *d_rew, const uint8_t *d_done, const float *d_info, double *d_row) {
+    CHECK_SIM(s);
+    if (n < 1) return fail(s, -1, "avr_episode_stats_device: n %d < 1", (int)n);
+    if (!d_rew || !d_done || !d_info) return fail(s, -1, "avr_episode_stats_device: d_rew, d_done and d_info must be given");
+    if (int r = train_stats_state(s, false)) return r;
+    HIPCHK(s, avr_launch_episode_stats(d_rew, d_done, d_info, n, s->cfg.n_envs, s->d_ts_env, s->d_ts_part, s->d_ts_row, d_row, s->stream));
+    return 0;
+}
+
+int avr_train_stats_buffers(avr_sim *s, double **d_R, double **d_rms, void **d_env, double **d_row) {
+    CHECK_SIM(s);
+    if (int r = train_stats_state(s, false)) return r;
+    if (d_R) *d_R = s->d_ts_R;
+    if (d_rms) *d_rms = s->d_ts_rms;
+    if (d_env) *d_env = s->d_ts_env;
+    if (d_row) *d_row = s->d_ts_row;
     return 0;
 }
 

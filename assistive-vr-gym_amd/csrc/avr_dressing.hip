@@ -931,6 +931,22 @@ int32_t avr_ppo_words(void) { return 0; }
 void *avr_policy_block(avr_sim *s) { (void)s; return nullptr; }
 int avr_policy_get(avr_sim *s, avr_policy_out *out) { (void)out; DRESS_NO_PPO; }
 int avr_policy_obs_norm_device(avr_sim *s, const float *d_mean, const float *d_var) { (void)d_mean; (void)d_var; DRESS_NO_PPO; }
+// (reward normalisation and episode statistics consume the policy rollouts' stacked arrays, avr_trainstats.hip)
+#define DRESS_NO_TRAIN_STATS return fail(s, -1, "training statistics: not built for DressingJaco")
+int avr_reward_norm_device(avr_sim *s, int32_t n, double gamma, double clip_rew, double eps, int32_t update, const float *d_rew,
+                           const uint8_t *d_done, float *d_rew_out) {
+    (void)n; (void)gamma; (void)clip_rew; (void)eps; (void)update; (void)d_rew; (void)d_done; (void)d_rew_out;
+    DRESS_NO_TRAIN_STATS;
+}
+int avr_episode_stats_device(avr_sim *s, int32_t n, const float *d_rew, const uint8_t *d_done, const float *d_info, double *d_row) {
+    (void)n; (void)d_rew; (void)d_done; (void)d_info; (void)d_row;
+    DRESS_NO_TRAIN_STATS;
+}
+int avr_train_stats_reset(avr_sim *s) { DRESS_NO_TRAIN_STATS; }
+int avr_train_stats_buffers(avr_sim *s, double **d_R, double **d_rms, void **d_env, double **d_row) {
+    (void)d_R; (void)d_rms; (void)d_env; (void)d_row;
+    DRESS_NO_TRAIN_STATS;
+}
 int avr_step(avr_sim *s, const float *act, float *obs, float *rew, uint8_t *done, float *info) {
     CHECK_SIM(s);
     const size_t E = (size_t)s->cfg.n_envs;

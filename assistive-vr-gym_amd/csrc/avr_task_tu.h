@@ -27,5 +27,6 @@ namespace AVR_NS {
 #include "avr_policy.hip"
 #include "avr_rollover.hip"
 #include "avr_ppo.hip"
+#include "avr_trainstats.hip"
 #include "avr_capi.hip"
 }  // namespace AVR_NS

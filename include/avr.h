@@ -299,6 +299,64 @@ int avr_policy_get(avr_sim *sim, avr_policy_out *out);
  *   policy has no ob_rms. */
 int avr_policy_obs_norm_device(avr_sim *sim, const float *d_mean, const float *d_var);
 
+/* ---- reward normalisation and episode statistics on the device (FeedingJaco, ScratchItchPR2, BedBathingPR2;
+ * DressingJaco: -1) ----
+ * With the device rollover an env finishes and restarts inside a rollout and the host never sees an episode
+ * end; these calls read the stacked arrays d_rew[n][n_envs], d_done[n][n_envs], d_info[n][n_envs]
+ * [AVR_INFO_DIM] of avr_rollout_policy_device once and carry per-env state across calls in the handle, so an
+ * episode may span any number of calls and an env may finish several times in one (csrc/avr_trainstats.hip;
+ * avr/ppo.py reward_norm_reference / episode_stats_reference are the readable mirrors).  All are asynchronous
+ * on avr_stream(sim) and belong outside any graph (a scratch buffer grows with n).  No atomics, every
+ * reduction in double in a fixed order: the same call on the same inputs and carried state gives the same
+ * bits.  The carried rows are allocated and reset by the first call of any of them.
+ *
+ * avr_reward_norm_device: the reward half of baselines' VecNormalize (the pipeline of the checkpoints
+ *   enjoy_vr.py loads; the observation half is ob_rms, avr_policy_obs_norm_device).  R[n_envs] is the
+ *   discounted return, a double row; (mean, var, count) its running moments, three doubles starting at
+ *   (0, 1, 1e-4).  For k = 0 .. n-1 in order, in double:
+ *     R[e]  = R[e] * gamma + rew[k][e]
+ *     if update: bm = mean_e R, bv = mean_e (R - bm)^2, bc = n_envs
+ *                d = bm - mean; tot = count + bc
+ *                new_mean = mean + d * bc / tot
+ *                var  = (var * count + bv * bc + d * d * count * bc / tot) / tot
+ *                mean = new_mean; count = tot
+ *     rew_out[k][e] = (float) clamp(rew[k][e] / sqrt(var + eps), -clip_rew, clip_rew)
+ *     if done[k][e]: R[e] = 0
+ *   A step's rewards are scaled with the statistics after that step's update and R is zeroed after it, as
+ *   baselines does.  update = 0 is eval mode: R and the statistics stay untouched, only the scaling runs.
+ *   d_rew_out may equal d_rew.  Errors: n < 1, a NULL pointer, gamma outside [0, 1], eps <= 0, clip_rew < 0.
+ * avr_episode_stats_device: per env the running episode's return (float32, rewards added in ascending k),
+ *   length and summed info[..][0] (total_force_on_human, float32).  At done[k][e] the episode closes with
+ *   return ep_ret, length ep_len, success info[k][e][1] and mean force ep_force / ep_len (in double); the
+ *   three are kept as the env's last finished episode, its counter of finished episodes goes up, and the
+ *   accumulators restart at zero.  d_row (NULL: not wanted; the handle keeps the row either way) receives
+ *   this call's aggregate over all episodes closed in it, AVR_EPSTAT_WORDS doubles:
+ *     {episodes, ret_sum, ret_sumsq, ret_min, ret_max, len_sum, success_sum, force_mean_sum,
+ *      steps = n * n_envs, rew_sum = the sum of all n * n_envs rewards}
+ *   each env's share added in ascending k, the envs folded on a fixed tree.  With no episode closed ret_min
+ *   = +inf and ret_max = -inf.  Errors: n < 1, d_rew / d_done / d_info NULL.
+ * avr_train_stats_reset: allocate (first call) all carried rows, zero them, set the moments to (0, 1, 1e-4)
+ *   and the handle's aggregate row to that of a call without episodes.
+ * avr_train_stats_buffers: device pointers owned by the handle (any may be NULL; allocates and resets like
+ *   the other calls when none has run): d_R[n_envs], d_rms[3] = (mean, var, count), d_env: the per-env
+ *   episode rows, [AVR_EPENV_ROWS][n_envs] 4-byte words (float32 or int32 by row, AVR_EPENV_*), d_row
+ *   [AVR_EPSTAT_WORDS] the last call's aggregate (what a checkpoint or a merge across ranks reads: the
+ *   moments merge by the formula above). */
+#define AVR_EPSTAT_WORDS 10
+#define AVR_EPENV_ROWS 7
+#define AVR_EPENV_RET 0           /* float32: the running episode's return so far           */
+#define AVR_EPENV_LEN 1           /* int32:   its length so far                              */
+#define AVR_EPENV_FORCE 2         /* float32: its summed total_force_on_human                */
+#define AVR_EPENV_LAST_RET 3      /* float32: the last finished episode's return             */
+#define AVR_EPENV_LAST_LEN 4      /* int32:   its length                                     */
+#define AVR_EPENV_LAST_SUCCESS 5  /* float32: its task_success                               */
+#define AVR_EPENV_FINISHED 6      /* int32:   episodes finished since avr_train_stats_reset  */
+int avr_reward_norm_device(avr_sim *sim, int32_t n, double gamma, double clip_rew, double eps, int32_t update, const float *d_rew,
+                           const uint8_t *d_done, float *d_rew_out);
+int avr_episode_stats_device(avr_sim *sim, int32_t n, const float *d_rew, const uint8_t *d_done, const float *d_info, double *d_row);
+int avr_train_stats_reset(avr_sim *sim);
+int avr_train_stats_buffers(avr_sim *sim, double **d_R, double **d_rms, void **d_env, double **d_row);
+
 /* ---- human height variants inside one handle (FeedingJaco, ScratchItchPR2, BedBathingPR2; DressingJaco: -1) ----
  * The reference's *New-v0 ids draw a new hipbone_to_mouth_height at every reset (feeding.py:170-172) and
  * rebuild the human (human_creation.py); here a handle holds a finite set of height variants and every env
