@@ -277,9 +277,10 @@ def test_padding_stays_zero(feeding):
 
 
 # ------------------------------------------------------------------ 4. Adam and clipping
-def torch_update(pol, rms, batch, params, epochs, M, dtype):
+def torch_update(pol, rms, batch, params, epochs, M, dtype, clip=True):
     """epochs x M {loss; backward; clip_grad_norm_; Adam.step} on a copy of pol in dtype (identity
-    permutation); returns ({key: weights}, [statistics per minibatch])."""
+    permutation); returns ({key: weights}, [statistics per minibatch]).  clip False: Adam on the
+    gradient as it is (max_grad_norm <= 0 on the device); grad_norm is still the gradient's norm."""
     import copy
     import torch
     from avr import ppo
@@ -294,7 +295,10 @@ def torch_update(pol, rms, batch, params, epochs, M, dtype):
             opt.zero_grad()
             loss, st = ppo.ppo_loss_reference(p, rms, b, torch.arange(j * B, (j + 1) * B), params)
             loss.backward()
-            st['grad_norm'] = torch.nn.utils.clip_grad_norm_(p.parameters(), params['max_grad_norm'])
+            if clip:
+                st['grad_norm'] = torch.nn.utils.clip_grad_norm_(p.parameters(), params['max_grad_norm'])
+            else:
+                st['grad_norm'] = torch.sqrt(sum((q.grad ** 2).sum() for q in p.parameters()))
             opt.step()
             rows.append({k: float(v) for k, v in st.items()})
     named = ppo.module_params(p)
