@@ -26,10 +26,13 @@ EXPORTS = [
     'avr_human_variants_set', 'avr_human_variants', 'avr_human_variant_info', 'avr_narrowphase_query_slots',
     'avr_gae_device', 'avr_ppo_reset', 'avr_ppo_grad_device', 'avr_ppo_adam_device', 'avr_ppo_update_device', 'avr_ppo_buffers',
     'avr_ppo_words', 'avr_policy_block', 'avr_policy_get', 'avr_policy_obs_norm_device',
+    'avr_ppo_advstat_device', 'avr_ppo_grad_segment_device', 'avr_ppo_combine_device',
     'avr_reward_norm_device', 'avr_episode_stats_device', 'avr_train_stats_reset', 'avr_train_stats_buffers',
 ]
 PPO_STAT_WORDS, PPO_STATS_ROWS = 8, 256      # include/avr.h AVR_PPO_STAT_WORDS, AVR_PPO_STATS_ROWS
 PPO_STATS = ('policy_loss', 'value_loss', 'entropy', 'approx_kl', 'clip_frac', 'grad_norm')   # a statistics row's first words
+PPO_SEGMENTS = 8             # include/avr.h AVR_PPO_SEGMENTS: segments of a minibatch, whatever the rank count
+PPO_SEG_WORDS = 13144 + PPO_STAT_WORDS       # include/avr.h AVR_PPO_SEG_WORDS: the weight block's words, then a statistics row's
 # include/avr.h AVR_EPSTAT_WORDS: the columns of avr_episode_stats_device's aggregate row (float64)
 EPISODE_STATS = ('episodes', 'ret_sum', 'ret_sumsq', 'ret_min', 'ret_max', 'len_sum', 'success_sum', 'force_mean_sum', 'steps', 'rew_sum')
 EPSTAT_WORDS = len(EPISODE_STATS)
@@ -140,6 +143,10 @@ def load(path=LIB_PATH):
         lib.avr_policy_block.restype = vp
         lib.avr_policy_get.argtypes = [vp, C.POINTER(avr_policy_out)]
         lib.avr_policy_obs_norm_device.argtypes = [vp, vp, vp]
+    if hasattr(lib, 'avr_ppo_combine_device'):      # (absent in experiment builds of older trees)
+        lib.avr_ppo_advstat_device.argtypes = [vp, C.POINTER(avr_ppo_batch)]
+        lib.avr_ppo_grad_segment_device.argtypes = [vp, C.POINTER(avr_ppo_batch), C.POINTER(avr_ppo_params), C.c_int32, C.c_int32, vp, C.c_int32, vp]
+        lib.avr_ppo_combine_device.argtypes = [vp, C.POINTER(avr_ppo_params), vp]
     if hasattr(lib, 'avr_train_stats_reset'):       # (absent in experiment builds of older trees)
         lib.avr_reward_norm_device.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, vp, vp, vp]
         lib.avr_episode_stats_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
@@ -467,6 +474,20 @@ class Sim:
     def ppo_update_device(self, batch, params, epochs, n_minibatch, d_perm=None):
         """epochs x n_minibatch {gradient; Adam} with no host synchronisation (d_perm: int32 [epochs, N])."""
         self._chk(self.lib.avr_ppo_update_device(self.h, C.byref(batch), C.byref(params), int(epochs), int(n_minibatch), d_perm))
+
+    def ppo_advstat_device(self, batch):
+        """The batch's advantage mean / std into the handle's cache (what minibatch 0 of ppo_grad_device computes)."""
+        self._chk(self.lib.avr_ppo_advstat_device(self.h, C.byref(batch)))
+
+    def ppo_grad_segment_device(self, batch, params, minibatch, n_minibatch, d_perm, segment, d_seg):
+        """Segment `segment` (of PPO_SEGMENTS) of a minibatch: its share of the gradient and of the statistics
+        into the device row d_seg [PPO_SEG_WORDS]; the handle's gradient block is not touched."""
+        self._chk(self.lib.avr_ppo_grad_segment_device(self.h, C.byref(batch), C.byref(params), int(minibatch), int(n_minibatch), d_perm, int(segment), d_seg))
+
+    def ppo_combine_device(self, params, d_segs):
+        """The handle's gradient block and next statistics row from the device rows d_segs [PPO_SEGMENTS,
+        PPO_SEG_WORDS], added in ascending segment order in double; ppo_adam_device follows."""
+        self._chk(self.lib.avr_ppo_combine_device(self.h, C.byref(params), d_segs))
 
     def ppo_buffers(self):
         """Device pointers (grad, m, v: ppo_words() float32 each; stats [PPO_STATS_ROWS, PPO_STAT_WORDS])."""

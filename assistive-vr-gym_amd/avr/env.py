@@ -550,13 +550,29 @@ class AVRTorchVecEnv(AVRVecEnv):
     the handle's rollover mode on.  From then on a finished env takes a pool state on the device: step()
     neither synchronises nor resets on the host, and rollout_policy runs any n steps across episode
     boundaries in one call.  Episodes then re-use the pool's initial states instead of drawing new ones
-    (DESIGN.md).  pool_build_s holds the time the pool took to build."""
+    (DESIGN.md).  pool_build_s holds the time the pool took to build.
 
-    def __init__(self, *args, reset_pool=None, **kw):
+    pool_world=(rank, world, group) (with reset_pool=m, one env per rank of a torch.distributed group, this
+    one holding the global env ids [rank * n_envs, (rank + 1) * n_envs), i.e. env_offset = rank * n_envs):
+    the ranks all-gather the pool rows they built before installing them, so every rank holds the same
+    m * world * n_envs rows in the order one process of world * n_envs envs builds them (episode-major,
+    global env within the episode), and a rollover picks the same state at any world size."""
+
+    def __init__(self, *args, reset_pool=None, pool_world=None, **kw):
         if reset_pool is not None and (int(reset_pool) != reset_pool or int(reset_pool) < 1):
             raise ValueError('reset_pool must be None or an integer >= 1, not %r' % (reset_pool,))
         self.reset_pool = None if reset_pool is None else int(reset_pool)
+        if pool_world is not None:
+            if self.reset_pool is None:
+                raise ValueError('pool_world needs reset_pool=m')
+            rank, world, _ = pool_world
+            if not 0 <= int(rank) < int(world):
+                raise ValueError('pool_world: rank %r outside 0..%r' % (rank, int(world) - 1))
+        self.pool_world = pool_world
         super().__init__(*args, **kw)
+        if pool_world is not None and self.env_offset != int(pool_world[0]) * self.n:
+            self.sim.close()
+            raise ValueError('pool_world: rank %d of %d envs each needs env_offset=%d, not %d' % (pool_world[0], self.n, pool_world[0] * self.n, self.env_offset))
         if self.reset_pool and self.task == ABI.TASK_DRESSING:
             self.sim.close()
             raise NotImplementedError('reset_pool: the device rollover is not built for DressingJaco-v0')
@@ -592,7 +608,14 @@ class AVRTorchVecEnv(AVRVecEnv):
             self._reset_rows(every)
             S.append(self.sim.get_state())
             O.append(self._obs.copy())
-        self.sim.reset_pool_set(np.concatenate(S), np.concatenate(O))
+        S, O = np.stack(S), np.stack(O)                     # [m, n_envs, ...]
+        if self.pool_world is not None and int(self.pool_world[1]) > 1:
+            # every rank's rows, in global env order within each episode: the pool one process of all the envs builds
+            from . import dist as D
+            torch, group = self.torch, self.pool_world[2]
+            S = D.gather_stacked(torch.from_numpy(S).to(self.dev), group).cpu().numpy()
+            O = D.gather_stacked(torch.from_numpy(O).to(self.dev), group).cpu().numpy()
+        self.sim.reset_pool_set(S.reshape(-1, S.shape[-1]), O.reshape(-1, O.shape[-1]))
         self.sim.rollover_enable(True)
         self.sim.rollover_set_episodes(self.episode)
         to, tv, ep = self.sim.rollover_buffers()

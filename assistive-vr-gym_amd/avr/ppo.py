@@ -1,5 +1,6 @@
 """PPO on the batched backend: the readable references of the device update (csrc/avr_ppo.hip,
-include/avr.h avr_gae_device / avr_ppo_*) and a small trainer around AVRTorchVecEnv.
+include/avr.h avr_gae_device / avr_ppo_*), a small trainer around AVRTorchVecEnv (PPOTrainer) and its
+form across the ranks of a torch.distributed group (DistPPOTrainer, combine_reference).
 
 The loss is a2c_ppo_acktr's PPO.update (clipped surrogate, clipped value loss, entropy bonus) on the
 harness's ActorCritic (avr/policy_eval.py); the reference ships neither that library nor its
@@ -258,6 +259,39 @@ def ppo_loss_reference(actor_critic, ob_rms, batch, idx, params):
     return loss, stats
 
 
+PPO_SEGMENTS = 8                                    # include/avr.h AVR_PPO_SEGMENTS
+PPO_SEG_WORDS = PW_WORDS + 8                        # include/avr.h AVR_PPO_SEG_WORDS: the gradient block, then a statistics row
+
+
+def combine_reference(rows, ent_coef=0.0, act_dim=0):
+    """The host mirror of avr_ppo_combine_device's sum: rows [PPO_SEGMENTS, words] float32 -> [words]
+    float32, every word the rows' words added in ascending row order in float64 and rounded to float32
+    once; ent_coef is then subtracted, in float32, on the act_dim logstd words (rows of at least the
+    weight block's length).  The order is part of the definition: float64 addition is not associative,
+    and the one rounding to float32 can land on the other side of a tie."""
+    rows = np.asarray(rows)
+    assert rows.dtype == np.float32 and rows.ndim == 2 and rows.shape[0] == PPO_SEGMENTS
+    a = np.zeros(rows.shape[1], np.float64)
+    for k in range(PPO_SEGMENTS):
+        a = a + rows[k].astype(np.float64)
+    g = a.astype(np.float32)
+    if act_dim:
+        g[PW_LOGSTD:PW_LOGSTD + act_dim] = g[PW_LOGSTD:PW_LOGSTD + act_dim] - np.float32(ent_coef)
+    return g
+
+
+def segments_of(rank, world):
+    """The segments (of PPO_SEGMENTS) rank `rank` of `world` computes: a contiguous run of PPO_SEGMENTS /
+    world, rank 0's first, so that the ranks' rows gathered in rank order are in segment order."""
+    rank, world = int(rank), int(world)
+    if world < 1 or PPO_SEGMENTS % world:
+        raise ValueError('a world of %d ranks does not divide the %d segments of a minibatch (1, 2, 4 or 8 ranks)' % (world, PPO_SEGMENTS))
+    if not 0 <= rank < world:
+        raise ValueError('rank %d outside 0..%d' % (rank, world - 1))
+    per = PPO_SEGMENTS // world
+    return list(range(rank * per, (rank + 1) * per))
+
+
 def flatten_rollout(out, adv, ret):
     """rollout_policy's stacked tensors as ppo_loss_reference's flattened batch (views, no copy)."""
     n, E = out['rew'].shape
@@ -389,3 +423,105 @@ class PPOTrainer:
         in evaluate(..., fused=True)."""
         self.sync_module()
         PE.save_policy(path, self.actor_critic, self.ob_rms)
+
+
+class DistPPOTrainer(PPOTrainer):
+    """PPOTrainer across the ranks of a torch.distributed group: every rank steps its shard of the global
+    env ids (an env made with env_offset = rank * n_envs, reset_pool=m and pool_world=(rank, world,
+    group)), and all ranks end every iteration with the same weights, bit for bit the weights one process
+    with all world * n_envs envs computes.  PPOTrainer's arguments and hyper-parameters,
+    plus group: a torch.distributed process group (torch.distributed.group.WORLD for the default one);
+    None runs every segment locally with no collective: the single-process reference.
+
+    iterate(): the rollout and advantage estimation on the shard; the all-gather of obs, act, logp,
+    value, adv, ret (and rew, done) in global env order; the running observation statistics from the
+    gathered observations; the advantage statistics of the gathered batch; then, per epoch and
+    minibatch, this rank's PPO_SEGMENTS / world segment rows (avr_ppo_grad_segment_device), the
+    all-gather of the rows, avr_ppo_combine_device and avr_ppo_adam_device on inputs that are identical
+    on every rank.  The minibatch permutations come from `generator`, which must be seeded alike on all
+    ranks (None: a generator seeded with the env's seed).  'episodes' rows are gathered and added
+    (ret_min / ret_max: min / max), 'mean_reward' is the gathered rollout's.
+
+    norm_reward=True is not built: the return statistics reduce over the handle's own envs in a fixed
+    tree, which a shard cannot reproduce.  A world that does not divide PPO_SEGMENTS is a ValueError."""
+
+    def __init__(self, env, actor_critic, ob_rms=None, n_steps=128, generator=None, group=None, **hyper):
+        if hyper.get('norm_reward', DEFAULTS['norm_reward']):
+            raise NotImplementedError('DistPPOTrainer: norm_reward=True (the return statistics are per handle; see DESIGN.md)')
+        self.group = group
+        self.rank, self.world = (0, 1)
+        if group is not None:
+            from . import dist as D
+            self.rank, self.world = D.rank_world(group)
+        self.segments = segments_of(self.rank, self.world)
+        super().__init__(env, actor_critic, ob_rms, n_steps, generator, **hyper)
+        if self.generator is None:
+            self.generator = torch.Generator(device=env.dev).manual_seed(env.seed)
+        self._segs = torch.zeros(PPO_SEGMENTS, PPO_SEG_WORDS, device=env.dev)       # the minibatch's rows, in segment order
+
+    def _gather_batch(self, out, adv, ret):
+        """The shard's stacked arrays as one packed [n, E, C] tensor, gathered to [n, world * E, C] and
+        split into the flattened batch's contiguous tensors (copies only: no arithmetic touches a value)."""
+        n = out['n']
+        od, ad = out['obs'].shape[-1], out['act'].shape[-1]
+        cols = [out['obs'][:n], out['act'], out['logp'][..., None], out['value'][:n, :, None], adv[..., None], ret[..., None], out['rew'][..., None],
+                out['done'].to(torch.float32)[..., None]]
+        x = torch.cat(cols, -1)
+        if self.group is not None:
+            from . import dist as D
+            x = D.gather_stacked(x, self.group)
+        E = x.shape[1]
+        o = od + ad
+        G = dict(obs=x[..., :od], act=x[..., od:o], logp=x[..., o], value=x[..., o + 1], adv=x[..., o + 2], ret=x[..., o + 3], rew=x[..., o + 4])
+        G = {k: v.contiguous() for k, v in G.items()}
+        G['done'] = (x[..., o + 5] != 0).to(torch.uint8)
+        G['n'], G['E'] = n, E
+        return G
+
+    def iterate(self):
+        """One iteration (the class docstring's steps).  Returns what PPOTrainer.iterate returns, on every
+        rank alike; self.last additionally holds the gathered batch under 'gathered'."""
+        from . import _lib, dist as D
+        h, env = self.hyper, self.env
+        sim, cur = env.sim, torch.cuda.current_stream(env.dev)
+        out = env.rollout_policy(None, None, self.n_steps)
+        adv, ret = env.compute_gae(out, h['gamma'], h['lam'], h['bootstrap'])
+        res = {}
+        if h['episode_stats']:
+            row = env.episode_stats(out)
+            if self.group is not None:
+                rows = D.gather_rows(row[None], self.group)
+                row = rows.sum(0)
+                i0, i1 = _lib.EPISODE_STATS.index('ret_min'), _lib.EPISODE_STATS.index('ret_max')
+                row[i0], row[i1] = rows[:, i0].min(), rows[:, i1].max()
+            res['episodes'] = row
+        G = self._gather_batch(out, adv, ret)
+        n, E = G['n'], G['E']
+        N = n * E
+        if h['update_ob_rms']:
+            self._update_ob_rms(G['obs'])
+        epochs, M = int(h['epochs']), int(h['n_minibatch'])
+        if getattr(env, '_ppo_stats', None) is None:
+            env.ppo_reset()
+        perm = torch.stack([torch.randperm(N, device=env.dev, generator=self.generator) for _ in range(epochs)]).to(torch.int32).contiguous()
+        batch = sim.ppo_batch(n, E, **{k: G[k].data_ptr() for k in ('obs', 'act', 'logp', 'value', 'adv', 'ret')})
+        P = sim.ppo_params(h)
+        mine = self._segs if self.group is None else self._segs[self.segments[0]:self.segments[-1] + 1]
+        env.ext.wait_stream(cur)
+        sim.ppo_advstat_device(batch)
+        for ep in range(epochs):
+            for j in range(M):
+                for i, sg in enumerate(self.segments):
+                    sim.ppo_grad_segment_device(batch, P, j, M, perm[ep].data_ptr(), sg, mine[i].data_ptr())
+                if self.group is not None:
+                    cur.wait_stream(env.ext)
+                    self._segs.copy_(D.gather_rows(mine, self.group))
+                    env.ext.wait_stream(cur)
+                sim.ppo_combine_device(P, self._segs.data_ptr())
+                sim.ppo_adam_device(P)
+        cur.wait_stream(env.ext)
+        rows = min(epochs * M, _lib.PPO_STATS_ROWS)
+        stats = env._ppo_stats[:rows, :len(_lib.PPO_STATS)].clone()
+        self.iterations += 1
+        self.last = dict(out=out, adv=adv, ret=ret, rew_norm=None, gathered=G, perm=perm)
+        return dict(res, stats=stats, mean_reward=G['rew'].mean())

@@ -56,6 +56,10 @@
     int avr_ppo_update_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t epochs,          \
                               int32_t n_minibatch, const int32_t *d_perm);                                         \
     int avr_ppo_buffers(avr_sim *s, float **d_grad, float **d_m, float **d_v, float **d_stats);                    \
+    int avr_ppo_advstat_device(avr_sim *s, const avr_ppo_batch *b);                                                \
+    int avr_ppo_grad_segment_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t minibatch, \
+                                    int32_t n_minibatch, const int32_t *d_perm, int32_t segment, float *d_seg);    \
+    int avr_ppo_combine_device(avr_sim *s, const avr_ppo_params *p, const float *d_segs);                          \
     int32_t avr_ppo_words(void);                                                                                   \
     void *avr_policy_block(avr_sim *s);                                                                            \
     int avr_policy_get(avr_sim *s, avr_policy_out *out);                                                           \
@@ -253,6 +257,12 @@ int avr_ppo_update_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_para
     DISPATCH(s, avr_ppo_update_device(h, b, p, epochs, m, perm));
 }
 int avr_ppo_buffers(avr_sim *s, float **g, float **m, float **v, float **st) { DISPATCH(s, avr_ppo_buffers(h, g, m, v, st)); }
+int avr_ppo_advstat_device(avr_sim *s, const avr_ppo_batch *b) { DISPATCH(s, avr_ppo_advstat_device(h, b)); }
+int avr_ppo_grad_segment_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t j, int32_t m, const int32_t *perm, int32_t seg,
+                                float *d_seg) {
+    DISPATCH(s, avr_ppo_grad_segment_device(h, b, p, j, m, perm, seg, d_seg));
+}
+int avr_ppo_combine_device(avr_sim *s, const avr_ppo_params *p, const float *d_segs) { DISPATCH(s, avr_ppo_combine_device(h, p, d_segs)); }
 int32_t avr_ppo_words(void) { return avr_feeding::avr_ppo_words(); }
 void *avr_policy_block(avr_sim *s) {
     if (!s || !s->impl) return nullptr;

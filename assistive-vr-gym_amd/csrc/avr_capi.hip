@@ -82,7 +82,8 @@ struct avr_sim {
     float *d_ppo_grad, *d_ppo_m, *d_ppo_v, *d_ppo_part, *d_ppo_stats, *d_ppo_advstat;
     double *d_ppo_spart, *d_ppo_advpart;
     int *d_ppo_step;
-    int ppo_row;                           // the statistics row the last gradient call wrote
+    int ppo_row;                           // the statistics row the last gradient (or combine) call wrote
+    int ppo_combines;                      // avr_ppo_combine_device calls since the last avr_ppo_advstat_device / avr_ppo_reset
     const float *ppo_adv;                  // the batch (adv pointer, sample count) whose advantage mean / std the
     long long ppo_adv_n;                   //   device holds (NULL: none)
     // reward normalisation and episode statistics (avr_train_stats_reset, avr_trainstats.hip): one block of
@@ -1353,6 +1354,7 @@ int avr_ppo_reset(avr_sim *s) {
     }
     HIPCHK(s, hipMemsetAsync(s->d_ppo_spart, 0, dw * sizeof(double) + fw * sizeof(float), s->stream));
     s->ppo_row = 0;
+    s->ppo_combines = 0;
     s->ppo_adv = nullptr; s->ppo_adv_n = 0;
     return 0;
 }
@@ -1430,6 +1432,58 @@ int avr_ppo_update_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_para
                 return r;
             if (int r = ppo_adam(s, p)) return r;
         }
+    return 0;
+}
+
+// ---- the update across ranks: a minibatch in AVR_PPO_SEGMENTS segments, their rows combined in a fixed order
+static_assert(PW_WORDS + PPO_STAT_WORDS == AVR_PPO_SEG_WORDS, "include/avr.h AVR_PPO_SEG_WORDS: the weight block plus a statistics row");
+
+int avr_ppo_advstat_device(avr_sim *s, const avr_ppo_batch *b) {
+    CHECK_SIM(s);
+    if (!s->d_ppo_grad) return fail(s, -1, "avr_ppo_advstat_device: no optimiser state (call avr_ppo_reset first)");
+    if (!b) return fail(s, -1, "avr_ppo_advstat_device: batch is NULL");
+    if (!b->adv) return fail(s, -1, "avr_ppo_advstat_device: the batch's adv must be given");
+    if (b->n < 1 || b->E < 1) return fail(s, -1, "avr_ppo_advstat_device: batch n %d / E %d < 1", (int)b->n, (int)b->E);
+    const long long N = (long long)b->n * b->E;
+    if (N > 0x7fffffffLL) return fail(s, -1, "avr_ppo_advstat_device: batch of %lld samples (int32 sample indices)", N);
+    HIPCHK(s, avr_launch_ppo_advstat(b->adv, N, s->d_ppo_advpart, s->d_ppo_advstat, s->stream));
+    s->ppo_adv = b->adv; s->ppo_adv_n = N;
+    s->ppo_combines = 0;                   // (a new batch: avr_ppo_combine_device's statistics rows start at 0)
+    return 0;
+}
+
+int avr_ppo_grad_segment_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t minibatch, int32_t n_minibatch, const int32_t *d_perm,
+                                int32_t segment, float *d_seg) {
+    CHECK_SIM(s);
+    const char *who = "avr_ppo_grad_segment_device";
+    if (!b) return fail(s, -1, "%s: batch is NULL", who);
+    if (int r = ppo_check(s, who, b, p, n_minibatch)) return r;
+    if (minibatch < 0 || minibatch >= n_minibatch) return fail(s, -1, "%s: minibatch %d outside 0..%d", who, (int)minibatch, (int)n_minibatch - 1);
+    if (segment < 0 || segment >= PPO_SEGMENTS) return fail(s, -1, "%s: segment %d outside 0..%d", who, (int)segment, PPO_SEGMENTS - 1);
+    if (!d_seg) return fail(s, -1, "%s: d_seg is NULL", who);
+    const long long N = (long long)b->n * b->E;
+    const int B = (int)(N / n_minibatch);
+    if (B % PPO_SEGMENTS) return fail(s, -1, "%s: a minibatch of %d samples does not divide into %d segments", who, B, PPO_SEGMENTS);
+    if (p->norm_adv && (s->ppo_adv != b->adv || s->ppo_adv_n != N))
+        return fail(s, -1, "%s: norm_adv without the advantage statistics of this batch (call avr_ppo_advstat_device first)", who);
+    PpoArgs A;
+    A.obs = b->obs; A.act = b->act; A.logp = b->logp; A.value = b->value; A.adv = b->adv; A.ret = b->ret;
+    A.perm = d_perm; A.N = N; A.B = B / PPO_SEGMENTS; A.base = (long long)minibatch * B + (long long)segment * A.B;
+    A.clip = p->clip; A.vf_coef = p->vf_coef; A.inv_B = 1.f / (float)B;        // (the whole minibatch's mean)
+    A.norm_adv = p->norm_adv != 0; A.clip_value = p->clip_value != 0;
+    // the row's last words: the reduce kernel writes the statistics it knows, the rest stay zero
+    HIPCHK(s, hipMemsetAsync(d_seg + PW_WORDS, 0, PPO_STAT_WORDS * sizeof(float), s->stream));
+    HIPCHK(s, avr_launch_ppo_grad(s->d_pol, A, 0.f, s->d_ppo_advstat, s->d_ppo_part, s->d_ppo_spart, d_seg, d_seg + PW_WORDS, s->stream));
+    return 0;
+}
+
+int avr_ppo_combine_device(avr_sim *s, const avr_ppo_params *p, const float *d_segs) {
+    CHECK_SIM(s);
+    if (int r = ppo_check(s, "avr_ppo_combine_device", nullptr, p, 1)) return r;
+    if (!d_segs) return fail(s, -1, "avr_ppo_combine_device: d_segs is NULL");
+    s->ppo_row = s->ppo_combines;
+    s->ppo_combines = (s->ppo_combines + 1) % PPO_STATS_ROWS;
+    HIPCHK(s, avr_launch_ppo_combine(d_segs, s->d_pol, p->ent_coef, s->d_ppo_grad, s->d_ppo_stats + (size_t)s->ppo_row * PPO_STAT_WORDS, s->stream));
     return 0;
 }
 

@@ -927,6 +927,13 @@ int avr_ppo_buffers(avr_sim *s, float **d_grad, float **d_m, float **d_v, float 
     (void)d_grad; (void)d_m; (void)d_v; (void)d_stats;
     DRESS_NO_PPO;
 }
+int avr_ppo_advstat_device(avr_sim *s, const avr_ppo_batch *b) { (void)b; DRESS_NO_PPO; }
+int avr_ppo_grad_segment_device(avr_sim *s, const avr_ppo_batch *b, const avr_ppo_params *p, int32_t minibatch, int32_t n_minibatch, const int32_t *d_perm,
+                                int32_t segment, float *d_seg) {
+    (void)b; (void)p; (void)minibatch; (void)n_minibatch; (void)d_perm; (void)segment; (void)d_seg;
+    DRESS_NO_PPO;
+}
+int avr_ppo_combine_device(avr_sim *s, const avr_ppo_params *p, const float *d_segs) { (void)p; (void)d_segs; DRESS_NO_PPO; }
 int32_t avr_ppo_words(void) { return 0; }
 void *avr_policy_block(avr_sim *s) { (void)s; return nullptr; }
 int avr_policy_get(avr_sim *s, avr_policy_out *out) { (void)out; DRESS_NO_PPO; }

@@ -24,6 +24,11 @@
 // PPO_MAX_BLOCKS), a function of the minibatch size alone.  The statistics and the gradient norm
 // are accumulated in double, in fixed trees.
 //
+// Across ranks (avr_ppo_grad_segment_device / avr_ppo_combine_device): the same two kernels run on an
+// eighth of a minibatch at a time and avr_ppo_combine_kernel adds the eight results in ascending
+// order in double, so ranks that share the eight segments among them arrive at the same gradient
+// bits as one process that computes all eight.
+//
 // Padding: hidden units beyond `hidden`, observation rows beyond K_OBS_DIM and head column 7
 // without a critic have zero inputs or zero outgoing weights, so every product that forms their
 // gradient has an exactly-zero factor and the sums are exactly zero; Adam then moves them by
@@ -35,6 +40,8 @@
 #define PPO_STAT_WORDS 8                          // floats per statistics row
 #define PPO_STATS_ROWS 256                        // statistics rows the handle keeps (a ring)
 #define PPO_ADV_BLOCKS 256                        // blocks (partials) of the advantage statistics, at most
+#define PPO_SEGMENTS AVR_PPO_SEGMENTS             // segments of a minibatch (avr_ppo_grad_segment_device): fixed, whatever the rank count
+#define PPO_SEG_WORDS (PW_WORDS + PPO_STAT_WORDS) // floats of a segment row: the gradient block, then a statistics row's words
 
 // one network's partial: [8] logstd, [8] head biases, [POL_H][8] head weights, then the network (PN_*)
 enum { PP_LOGSTD = 0, PP_BH = 8, PP_WH = 16, PP_NET = 16 + POL_H * 8, PPO_PART = PP_NET + PN_WORDS };
@@ -377,6 +384,41 @@ __global__ __launch_bounds__(256) void avr_ppo_reduce_kernel(const float *__rest
     }
 }
 
+// ------------------------------------------------------------------ the segments of a minibatch, combined
+// A minibatch is cut into PPO_SEGMENTS runs of consecutive minibatch positions; the two kernels above
+// run on one run at a time (A.B the run's length, A.inv_B the whole minibatch's, ent_coef 0) and write a
+// segment row: the weight block's PW_WORDS gradient words, then the reduce kernel's statistics words.
+// This kernel adds the rows of a minibatch: word w of `grad` is the sum of the rows' word w in ascending
+// segment order in double, rounded to fp32 once, with the entropy bonus's constant derivative on logstd
+// as avr_ppo_reduce_kernel adds it; the statistics likewise, H from the weights.  The count of segments
+// is a constant, so the sum does not depend on who computed which row.
+__global__ __launch_bounds__(256) void avr_ppo_combine_kernel(const float *__restrict__ segs, const float *__restrict__ W, float ent_coef,
+                                                              float *__restrict__ grad, float *__restrict__ stats) {
+#pragma clang fp contract(off)
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w < PW_WORDS) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < PPO_SEGMENTS; k++) a += (double)segs[(size_t)k * PPO_SEG_WORDS + w];
+        float g = (float)a;
+        if (w >= PW_LOGSTD && w < PW_LOGSTD + K_ACT_DIM) g = g - ent_coef;       // d(-ent_coef H) / d logstd_a
+        grad[w] = g;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 5) {
+        const int t = threadIdx.x;
+        float r;
+        if (t == PS_H) {
+            r = 0.f;
+            for (int a = 0; a < K_ACT_DIM; a++) r += 0.5f + 0.9189385332046727f + W[PW_LOGSTD + a];
+        } else {
+            double a = 0.0;
+            for (int k = 0; k < PPO_SEGMENTS; k++) a += (double)segs[(size_t)k * PPO_SEG_WORDS + PW_WORDS + t];
+            r = (float)a;
+        }
+        stats[t] = r;
+    }
+}
+
 // ------------------------------------------------------------------ gradient clipping and Adam
 struct PpoAdam { float max_grad_norm, lr, beta1, beta2, eps; };
 
@@ -452,6 +494,11 @@ hipError_t avr_launch_ppo_grad(const float *W, const PpoArgs &A, float ent_coef,
     const int nb = avr_ppo_blocks(A.B);
     hipLaunchKernelGGL(avr_ppo_grad_kernel, dim3(nb, 2), dim3(64), 0, stream, W, A, advstat, part, spart);
     hipLaunchKernelGGL(avr_ppo_reduce_kernel, dim3((PW_WORDS + 255) / 256), dim3(256), 0, stream, part, spart, nb, W, ent_coef, A.inv_B, grad, stats);
+    return hipGetLastError();
+}
+
+hipError_t avr_launch_ppo_combine(const float *segs, const float *W, float ent_coef, float *grad, float *stats, hipStream_t stream) {
+    hipLaunchKernelGGL(avr_ppo_combine_kernel, dim3((PW_WORDS + 255) / 256), dim3(256), 0, stream, segs, W, ent_coef, grad, stats);
     return hipGetLastError();
 }
 

@@ -274,6 +274,36 @@ int avr_ppo_adam_device(avr_sim *sim, const avr_ppo_params *params);
 int avr_ppo_update_device(avr_sim *sim, const avr_ppo_batch *batch, const avr_ppo_params *params, int32_t epochs, int32_t n_minibatch,
                           const int32_t *d_perm);
 int avr_ppo_buffers(avr_sim *sim, float **d_grad, float **d_m, float **d_v, float **d_stats);
+/* ---- the update across ranks: a minibatch in segments, combined in a fixed order ----
+ * A minibatch of B samples is cut into AVR_PPO_SEGMENTS segments of B / AVR_PPO_SEGMENTS consecutive
+ * minibatch positions.  The count is a constant: it never depends on how many ranks share the work.  Each
+ * rank computes the rows of its own segments, the ranks exchange the rows (an all-gather; the library makes
+ * no collective call itself), and every rank combines the same AVR_PPO_SEGMENTS rows in ascending order in
+ * double, so the gradient, and after avr_ppo_adam_device the weights, have the same bits on every rank and
+ * at every rank count that divides AVR_PPO_SEGMENTS, one process included.
+ * avr_ppo_advstat_device: the batch's advantage mean and (unbiased) standard deviation, with the kernels
+ *   and into the cache avr_ppo_grad_device's minibatch 0 uses (keyed by the adv pointer and sample count);
+ *   only batch->n, E and adv are read.  It also restarts avr_ppo_combine_device's statistics rows at 0.
+ * avr_ppo_grad_segment_device: avr_ppo_grad_device's two kernels on segment `segment` of minibatch
+ *   `minibatch`: samples d_perm[minibatch * B + segment * B / 8 + i], i < B / 8, each weighted 1 / B (the whole
+ *   minibatch's mean), with ent_coef taken as 0.  d_seg[AVR_PPO_SEG_WORDS] (device) receives the segment's
+ *   share of dL / dw in the weight block's layout (avr_ppo_words() floats), then AVR_PPO_STAT_WORDS floats in a
+ *   statistics row's layout: its share of L_pi, L_v, approx_kl and clip_frac (the H word holds the weights' H,
+ *   grad_norm and the rest 0).  The handle's d_grad and statistics rows are not touched.  Errors: those of
+ *   avr_ppo_grad_device, B not divisible by AVR_PPO_SEGMENTS, segment outside 0 .. AVR_PPO_SEGMENTS - 1,
+ *   d_seg NULL, norm_adv without avr_ppo_advstat_device (or a minibatch 0 of avr_ppo_grad_device) on this batch.
+ * avr_ppo_combine_device: d_segs[AVR_PPO_SEGMENTS][AVR_PPO_SEG_WORDS] (device, row k segment k's) into the
+ *   handle's d_grad: every word the sum of the rows' words in ascending segment order in double, rounded to
+ *   fp32 once, then params->ent_coef subtracted on the logstd words as avr_ppo_grad_device does; the
+ *   statistics row likewise (H from the weights), row c % AVR_PPO_STATS_ROWS of d_stats for the c-th call
+ *   since the last avr_ppo_advstat_device or avr_ppo_reset.  avr_ppo_adam_device follows it as it follows
+ *   avr_ppo_grad_device.  avr/ppo.py combine_reference is the host mirror. */
+#define AVR_PPO_SEGMENTS 8
+#define AVR_PPO_SEG_WORDS (13144 + AVR_PPO_STAT_WORDS)   /* avr_ppo_words() + AVR_PPO_STAT_WORDS */
+int avr_ppo_advstat_device(avr_sim *sim, const avr_ppo_batch *batch);
+int avr_ppo_grad_segment_device(avr_sim *sim, const avr_ppo_batch *batch, const avr_ppo_params *params, int32_t minibatch, int32_t n_minibatch,
+                                const int32_t *d_perm, int32_t segment, float *d_seg);
+int avr_ppo_combine_device(avr_sim *sim, const avr_ppo_params *params, const float *d_segs);
 /* Floats in the weight block (and in d_grad, d_m, d_v), and the block's device address (NULL before
  * avr_policy_set); the layout is csrc/avr_policy.hip's PW_* (avr/ppo.py mirrors it: the PW_* / PN_*
  * constants, block_live_mask, unpack_block). */
