@@ -28,7 +28,9 @@ EXPORTS = [
     'avr_ppo_words', 'avr_policy_block', 'avr_policy_get', 'avr_policy_obs_norm_device',
     'avr_ppo_advstat_device', 'avr_ppo_grad_segment_device', 'avr_ppo_combine_device',
     'avr_reward_norm_device', 'avr_episode_stats_device', 'avr_train_stats_reset', 'avr_train_stats_buffers',
+    'avr_n_bodies', 'avr_get_body_poses', 'avr_render_set_planes', 'avr_render_device', 'avr_render_tile_stats', 'avr_render_kernel_info',
 ]
+RENDER_TILE = 8              # csrc/avr_render.hip RD_TILE: a wavefront traces an 8 x 8 pixel tile
 PPO_STAT_WORDS, PPO_STATS_ROWS = 8, 256      # include/avr.h AVR_PPO_STAT_WORDS, AVR_PPO_STATS_ROWS
 PPO_STATS = ('policy_loss', 'value_loss', 'entropy', 'approx_kl', 'clip_frac', 'grad_norm')   # a statistics row's first words
 PPO_SEGMENTS = 8             # include/avr.h AVR_PPO_SEGMENTS: segments of a minibatch, whatever the rank count
@@ -82,6 +84,12 @@ class avr_human_variant(C.Structure):
     """include/avr.h avr_human_variant: one height variant's float32 records (host arrays)."""
     ARRAYS = ('shape_pose', 'shape_param', 'shape_aabb', 'body_aabb', 'body_threshold', 'hc_jpos', 'hc_inertia', 'bb_targets')
     _fields_ = [('gender', C.c_int32), ('height', C.c_float), ('n_gshapes', C.c_int32), ('n_hbodies', C.c_int32)] + [(k, C.c_void_p) for k in ARRAYS]
+
+
+class avr_camera(C.Structure):
+    """include/avr.h avr_camera."""
+    _fields_ = [('eye', C.c_float * 3), ('target', C.c_float * 3), ('up', C.c_float * 3), ('fov_y_deg', C.c_float), ('near', C.c_float),
+                ('far', C.c_float), ('width', C.c_int32), ('height', C.c_int32), ('body', C.c_int32), ('reserved', C.c_int32 * 3)]
 
 
 _LIB = None
@@ -152,6 +160,14 @@ def load(path=LIB_PATH):
         lib.avr_episode_stats_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
         lib.avr_train_stats_reset.argtypes = [vp]
         lib.avr_train_stats_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(lib, 'avr_render_device'):           # (absent in experiment builds of older trees)
+        lib.avr_n_bodies.argtypes = [vp]
+        lib.avr_n_bodies.restype = C.c_int32
+        lib.avr_get_body_poses.argtypes = [vp, vp]
+        lib.avr_render_set_planes.argtypes = [vp, C.c_int32, vp, vp]
+        lib.avr_render_device.argtypes = [vp, C.POINTER(avr_camera), C.c_int32, vp, vp, vp, vp]
+        lib.avr_render_tile_stats.argtypes = [vp, C.POINTER(avr_camera), C.c_int32, vp, vp]
+        lib.avr_render_kernel_info.argtypes = [vp, vp]
     lib.avr_sync.argtypes = [vp]
     lib.avr_stream.argtypes = [vp]
     lib.avr_stream.restype = vp
@@ -641,6 +657,62 @@ class Sim:
         out = np.zeros(self.n, np.int32)
         self._chk(self.lib.avr_get_flags(self.h, out.ctypes.data))
         return out
+
+    # ---- views (include/avr.h avr_render_device)
+    def n_bodies(self):
+        return int(self.lib.avr_n_bodies(self.h))
+
+    def body_poses(self):
+        """(n_envs, n_bodies, 7) world COM frame of every collision body at the current state: what the
+        renderer places the shapes at (p.getBasePositionAndOrientation / p.getLinkState for all bodies)."""
+        out = np.zeros((self.n, self.n_bodies(), 7), np.float32)
+        self._chk(self.lib.avr_get_body_poses(self.h, out.ctypes.data))
+        return out
+
+    def render_set_planes(self, planes4, shape_range2):
+        """Install the hulls' face planes: planes4 (n_planes, 4) rows (n, w) of n . x <= w in the shape's
+        frame, shape_range2 (n_shapes, 2) rows (first plane, count) (avr/render.py hull_planes)."""
+        p = np.ascontiguousarray(planes4, np.float32).reshape(-1, 4)
+        r = np.ascontiguousarray(shape_range2, np.int32).reshape(-1, 2)
+        self._chk(self.lib.avr_render_set_planes(self.h, int(len(p)), p.ctypes.data if len(p) else None, r.ctypes.data))
+
+    @staticmethod
+    def camera_struct(cam):
+        """avr_camera from an object with its fields (avr/render.py Camera) or from an avr_camera."""
+        if cam is None or isinstance(cam, avr_camera):
+            return cam
+        c = avr_camera(fov_y_deg=float(cam.fov_y_deg), near=float(cam.near), far=float(cam.far), width=int(cam.width), height=int(cam.height),
+                       body=int(cam.body))
+        for i in range(3):
+            c.eye[i], c.target[i], c.up[i] = float(cam.eye[i]), float(cam.target[i]), float(cam.up[i])
+        return c
+
+    def render_device(self, cam, env_ids, depth_ptr, id_ptr, rgb_ptr, n=None):
+        """Queue a render of envs env_ids (None: 0 .. n-1, n defaulting to all) through cam into the device
+        buffers depth [n, H, W] float32, id [n, H, W] int32, rgb [n, H, W, 3] uint8 (any may be None, not
+        all); asynchronous on the handle's stream."""
+        c = self.camera_struct(cam)
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        n = (self.n if n is None else int(n)) if ids is None else len(ids)
+        self._chk(self.lib.avr_render_device(self.h, None if c is None else C.byref(c), n, None if ids is None else ids.ctypes.data,
+                                             depth_ptr, id_ptr, rgb_ptr))
+
+    def render_tile_stats(self, cam, env_ids=None):
+        """(n, tiles_y, tiles_x, 2) int32: per 8 x 8 tile the shapes its culled list holds and the hull
+        planes one of its pixels tests (include/avr.h avr_render_tile_stats)."""
+        c = self.camera_struct(cam)
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        n = self.n if ids is None else len(ids)
+        ty, tx = -(-int(c.height) // RENDER_TILE), -(-int(c.width) // RENDER_TILE)
+        out = np.zeros((n, ty, tx, 2), np.int32)
+        self._chk(self.lib.avr_render_tile_stats(self.h, C.byref(c), n, None if ids is None else ids.ctypes.data, out.ctypes.data))
+        return out
+
+    def render_kernel_info(self):
+        """{kernel: dict(vgprs, lds_bytes, scratch_bytes)} of the two render kernels."""
+        out = np.zeros(8, np.int32)
+        self._chk(self.lib.avr_render_kernel_info(self.h, out.ctypes.data))
+        return {n: dict(vgprs=int(out[4 * i]), lds_bytes=int(out[4 * i + 2]), scratch_bytes=int(out[4 * i + 3])) for i, n in enumerate(('frames', 'trace'))}
 
     def kernel_info(self):
         """{kernel: dict(vgprs, lds_bytes, scratch_bytes)} of the step's kernels (include/avr.h)."""

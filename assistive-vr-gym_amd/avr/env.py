@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _abi as ABI
 from . import _lib
+from . import render as RD
 from . import reset as RS
 
 MAX_EPISODE_STEPS = 200          # assistive_gym/__init__.py TimeLimit
@@ -302,6 +303,8 @@ class AVRVecEnv:
             # origins stay, the device tables live in the handle
             recs = [MC.human_variant_records(ABI.SCENES[self.task], g, h, base=base_heights) for g, h in self.variants]
             self.sim.human_variants_set(recs)
+            for R in recs:                  # (render: the base scene's hull planes serve every variant)
+                RD.assert_variant_hulls(self.A, R['arrays'])
             self._variant_ctx = dict(slots={g: [2 + v for v, (vg, _) in enumerate(self.variants) if vg == g] for g in MC.GENDERS},
                                      pos={2 + v: R['human_pos'] for v, R in enumerate(recs)}, draw=height_draw)
         self.observation_space = Box(-1e9, 1e9, (self.L.OBS_DIM,))
@@ -530,6 +533,29 @@ class AVRVecEnv:
         self.sim.set_state(S)
         self.iteration[:] = np.asarray(S)[:, self.L.S_TASK + self.L.T_ITER].astype(np.int64)
 
+    # ------------------------------------------------------------------ views
+    def _camera(self, camera, width, height):
+        if self.task == ABI.TASK_DRESSING:
+            raise NotImplementedError('render: not built for DressingJaco-v0')
+        return (RD.default_camera(self.task) if camera is None else camera).resized(width, height)
+
+    def render(self, mode='rgb_array', envs=None, camera=None, width=320, height=240, outputs=('rgb',)):
+        """The envs as a camera sees their current state (include/avr.h avr_render_device): the
+        collision shapes, ray-cast on the device -- gym's render(mode='rgb_array'), which the reference
+        offers only as Bullet's GUI (env.py:613-620).  envs: the env indices (None: all; repeats
+        allowed), camera: a render.Camera (None: the task's GUI camera, render.default_camera), always taken
+        at width x height (the camera's own size is not used), outputs: some of 'rgb' [H, W, 3] uint8, 'depth' [H, W] float32 (metres along the
+        ray, inf for a miss), 'id' [H, W] int32 (shape index, render.shape_table; -1 for a miss).
+        Returns host arrays: one output alone, else a dict; with envs=None and one env [H, W, ...], the
+        gym contract, else stacked [n, H, W, ...].  Reads the state only: stepping is not affected."""
+        if mode != 'rgb_array':
+            raise NotImplementedError("render: mode %r; only 'rgb_array' (there is no GUI)" % (mode,))
+        cam = self._camera(camera, width, height)
+        out = RD.render_host(self.sim, self.A, cam, None if envs is None else np.asarray(envs, np.int32).reshape(-1), tuple(outputs), device=self.device)
+        if envs is None and self.n == 1:
+            out = {k: v[0] for k, v in out.items()}
+        return out[outputs[0]] if len(outputs) == 1 else out
+
     def close(self):
         if self._prefetch:
             self._prefetch.wait()
@@ -682,6 +708,29 @@ class AVRTorchVecEnv(AVRVecEnv):
                 obs = torch.where(m[:, None], torch.from_numpy(self._obs).to(self.dev), obs)
         self._cur = obs
         return obs, rew, done, info
+
+    def render_device(self, envs=None, camera=None, width=320, height=240, outputs=('rgb',)):
+        """render() with device tensors and no host synchronisation: the images of the state as the
+        steps queued so far leave it, in stream order with step() (the render waits for the caller's
+        stream, the caller's stream for the render; a first call, or one with more envs than any before,
+        allocates the handle's scratch, and an explicit env list is copied from host memory: include/avr.h
+        avr_render_device).  Returns {name: cuda tensor [n, H, W, ...]} for the
+        names in outputs ('rgb' uint8, 'depth' float32, 'id' int32)."""
+        torch = self.torch
+        cam = self._camera(camera, width, height)
+        bad = [o for o in outputs if o not in ('depth', 'id', 'rgb')]
+        if bad or not outputs:
+            raise ValueError("render_device: outputs must name some of 'depth', 'id', 'rgb', not %r" % (tuple(outputs),))
+        RD.install_planes(self.sim, self.A)
+        ids = None if envs is None else np.asarray(envs, np.int32).reshape(-1)
+        n = self.n if ids is None else len(ids)
+        H, W = int(cam.height), int(cam.width)
+        spec = {'depth': ((n, H, W), torch.float32), 'id': ((n, H, W), torch.int32), 'rgb': ((n, H, W, 3), torch.uint8)}
+        buf = {k: torch.empty(spec[k][0], dtype=spec[k][1], device=self.dev) for k in outputs}
+        self.ext.wait_stream(torch.cuda.current_stream(self.dev))
+        self.sim.render_device(cam, ids, *[buf[k].data_ptr() if k in buf else None for k in ('depth', 'id', 'rgb')], n=n)
+        torch.cuda.current_stream(self.dev).wait_stream(self.ext)
+        return buf
 
     # ------------------------------------------------------------------ device-resident policy rollouts
     def set_policy(self, actor_critic, ob_rms):
@@ -876,6 +925,10 @@ class AVREnv:
         i['task_success'] = int(i['task_success'])
         i['total_force_on_human'] = float(i['total_force_on_human'])
         return obs[0].astype(np.float64), float(rew[0]), bool(done[0]), i
+
+    def render(self, mode='rgb_array', **kw):
+        """gym's render(mode='rgb_array'): [height, width, 3] uint8 (AVRVecEnv.render's keywords)."""
+        return self.v.render(mode=mode, **kw)
 
     def close(self):
         self.v.close()

@@ -83,6 +83,14 @@
     int avr_get_link_pose(avr_sim *s, int32_t link, float *out7);                                                  \
     int avr_get_contact_summary(avr_sim *s, float *out4);                                                          \
     int avr_get_flags(avr_sim *s, int32_t *flags);                                                                 \
+    int32_t avr_n_bodies(avr_sim *s);                                                                              \
+    int avr_get_body_poses(avr_sim *s, float *out);                                                                \
+    int avr_render_set_planes(avr_sim *s, int32_t n_planes, const float *planes4, const int32_t *shape_range2);    \
+    int avr_render_device(avr_sim *s, const avr_camera *cam, int32_t n, const int32_t *env_ids, float *d_depth,     \
+                          int32_t *d_id, uint8_t *d_rgb);                                                          \
+    int avr_render_tile_stats(avr_sim *s, const avr_camera *cam, int32_t n, const int32_t *env_ids,                \
+                              int32_t *host_stats);                                                                \
+    int avr_render_kernel_info(avr_sim *s, int32_t *out8);                                                         \
     int avr_reset_ik(avr_sim *s, const uint8_t *mask, const float *h, const float *target7, const float *init,      \
                      const float *alt4, int32_t restarts, int32_t iters, float tol, const float *keepout8,          \
                      int32_t n_frames, float *host_obs, uint8_t *host_ok);                                         \
@@ -288,6 +296,16 @@ int avr_get_q(avr_sim *s, float *q, float *qd) { DISPATCH(s, avr_get_q(h, q, qd)
 int avr_get_link_pose(avr_sim *s, int32_t link, float *o) { DISPATCH(s, avr_get_link_pose(h, link, o)); }
 int avr_get_contact_summary(avr_sim *s, float *o) { DISPATCH(s, avr_get_contact_summary(h, o)); }
 int avr_get_flags(avr_sim *s, int32_t *f) { DISPATCH(s, avr_get_flags(h, f)); }
+int32_t avr_n_bodies(avr_sim *s) { DISPATCH(s, avr_n_bodies(h)); }
+int avr_get_body_poses(avr_sim *s, float *o) { DISPATCH(s, avr_get_body_poses(h, o)); }
+int avr_render_set_planes(avr_sim *s, int32_t n, const float *p4, const int32_t *r2) { DISPATCH(s, avr_render_set_planes(h, n, p4, r2)); }
+int avr_render_device(avr_sim *s, const avr_camera *cam, int32_t n, const int32_t *ids, float *d, int32_t *i, uint8_t *rgb) {
+    DISPATCH(s, avr_render_device(h, cam, n, ids, d, i, rgb));
+}
+int avr_render_tile_stats(avr_sim *s, const avr_camera *cam, int32_t n, const int32_t *ids, int32_t *st) {
+    DISPATCH(s, avr_render_tile_stats(h, cam, n, ids, st));
+}
+int avr_render_kernel_info(avr_sim *s, int32_t *o) { DISPATCH(s, avr_render_kernel_info(h, o)); }
 int avr_reset_ik(avr_sim *s, const uint8_t *m, const float *p, const float *t7, const float *init, const float *alt4, int32_t r, int32_t it,
                  float tol, const float *box8, int32_t n, float *o, uint8_t *ok) {
     DISPATCH(s, avr_reset_ik(h, m, p, t7, init, alt4, r, it, tol, box8, n, o, ok));

@@ -108,6 +108,18 @@ struct avr_sim {
     int var_gender[AVR_MAX_HUMAN_VARIANTS];
     float var_height[AVR_MAX_HUMAN_VARIANTS];
     int var_blocks;
+    // views (avr_render_device, avr_render.hip): the hulls' face planes and each shape's (first, count)
+    // range (avr_render_set_planes), the scene's shape kinds, and the grow-only scratch of a call: the
+    // resolved camera and shape records of every rendered env, the env ids, the tile statistics
+    const float *d_rd_hull_radius;         // [ns] largest |vertex| of each hull shape, 0 for the other kinds (avr_create)
+    float4 *d_rd_planes;
+    int2 *d_rd_range;
+    int rd_nplanes, rd_planes_set;
+    std::vector<int> h_shape_kind;
+    float *d_rd_scr;
+    size_t rd_scr_cap;
+    int *d_rd_ids;
+    size_t rd_ids_cap;
 };
 
 // Every entry point runs on the handle's device and restores the caller's current device on
@@ -390,6 +402,7 @@ int avr_create(const avr_config *cfg, const avr_model_desc *d, avr_sim **out) {
     if ((r = upload(s, ivec(d->shape_gender, ns), &k.shape_gender))) return r;
     s->h_shape_gender = ivec(d->shape_gender, ns);
     s->h_body_kind = ivec(d->body_kind, nb);
+    s->h_shape_kind = ivec(d->shape_kind, ns);
     if ((r = upload(s, ivec(d->shape_hull, (size_t)ns * 4), &k.shape_hull))) return r;
     if ((r = upload(s, cvt(d->shape_pose, 0, 7, 8, ns), &k.shape_pose))) return r;
     if ((r = upload(s, cvt(d->shape_param, (size_t)ns * 4), &k.shape_param))) return r;
@@ -407,6 +420,17 @@ int avr_create(const avr_config *cfg, const avr_model_desc *d, avr_sim **out) {
         for (int i = 0; i < d->n_hull_verts; i++)
             hv[i] = make_float4((float)d->hull_verts[3 * i], (float)d->hull_verts[3 * i + 1], (float)d->hull_verts[3 * i + 2], 0.f);
         if ((r = upload(s, hv, &k.hull_verts))) return r;
+        {   // the renderer's bounding radius of every hull, once per scene (avr_render.hip)
+            std::vector<float> hr((size_t)ns, 0.f);
+            for (int i = 0; i < ns; i++) {
+                if (d->shape_kind[i] != AVR_HULL) continue;
+                const int vs = d->shape_hull[4 * i], nv = d->shape_hull[4 * i + 1];
+                float r2 = 0.f;
+                for (int v = vs; v < vs + nv && v < d->n_hull_verts; v++) r2 = std::max(r2, hv[v].x * hv[v].x + hv[v].y * hv[v].y + hv[v].z * hv[v].z);
+                hr[i] = std::sqrt(r2) * 1.000001f;      // (rounded up: the radius only ever culls)
+            }
+            if ((r = upload(s, hr, &s->d_rd_hull_radius))) return r;
+        }
         // support tables for the large hulls (exact sub-linear support queries, avr_hulltab.cpp)
         std::vector<int> stab(ns, -1);
         std::vector<int2> cells;
@@ -705,6 +729,10 @@ int avr_destroy(avr_sim *s) {
     if (s->d_ik) (void)hipFree(s->d_ik);
     if (s->d_bs) (void)hipFree(s->d_bs);
     if (s->d_ts_scr) (void)hipFree(s->d_ts_scr);
+    if (s->d_rd_planes) (void)hipFree(s->d_rd_planes);
+    if (s->d_rd_range) (void)hipFree(s->d_rd_range);
+    if (s->d_rd_scr) (void)hipFree(s->d_rd_scr);
+    if (s->d_rd_ids) (void)hipFree(s->d_rd_ids);
     for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
     for (int i = 0; i < s->ngroups; i++) {
         if (s->gstream[i]) (void)hipStreamDestroy(s->gstream[i]);
@@ -1772,6 +1800,145 @@ int avr_get_flags(avr_sim *s, int32_t *flags) {
     HIPCHK(s, avr_launch_get_flags(s->d_state, (int *)d, E, s->stream));
     HIPCHK(s, hipMemcpyAsync(flags, d, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(s, hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------ views (avr_render.hip)
+int32_t avr_n_bodies(avr_sim *s) { return s ? s->km.nb : 0; }
+
+int avr_get_body_poses(avr_sim *s, float *out) {
+    CHECK_SIM(s);
+    if (!out) return fail(s, -1, "avr_get_body_poses: out is NULL");
+    const int E = s->cfg.n_envs, nb = s->km.nb;
+    float *d = nullptr;
+    if (query_buf(s, (size_t)7 * nb * E, &d)) return -3;
+    RdCam c;
+    memset(&c, 0, sizeof(c));
+    c.body = -1;
+    HIPCHK(s, avr_launch_render_frames(s->d_km, s->d_state, nullptr, E, E, c, s->d_rd_hull_radius, nullptr, d, s->stream));
+    HIPCHK(s, hipMemcpyAsync(out, d, (size_t)7 * nb * E * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+int avr_render_set_planes(avr_sim *s, int32_t n_planes, const float *planes4, const int32_t *shape_range2) {
+    CHECK_SIM(s);
+    const int ns = s->km.ns;
+    if (n_planes < 0 || (n_planes > 0 && !planes4) || !shape_range2) return fail(s, -1, "avr_render_set_planes: NULL array or negative plane count");
+    for (int i = 0; i < ns; i++) {
+        const int p0 = shape_range2[2 * i], np = shape_range2[2 * i + 1];
+        const bool hull = s->h_shape_kind[i] == AVR_HULL;
+        if (p0 < 0 || np < 0 || (long long)p0 + np > n_planes || (hull ? np < 4 : np != 0))
+            return fail(s, -1, "avr_render_set_planes: shape %d (%s) has plane range (%d, %d) of %d planes", i, hull ? "hull" : "no hull", p0, np,
+                        (int)n_planes);
+    }
+    for (size_t i = 0; i < (size_t)4 * n_planes; i++)
+        if (!std::isfinite(planes4[i])) return fail(s, -1, "avr_render_set_planes: plane %zu is not finite", i / 4);
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    if (s->d_rd_planes) HIPCHK(s, hipFree(s->d_rd_planes));
+    s->d_rd_planes = nullptr;
+    s->rd_planes_set = 0;
+    HIPCHK(s, hipMalloc(&s->d_rd_planes, (size_t)std::max(n_planes, 1) * sizeof(float4)));
+    if (!s->d_rd_range) HIPCHK(s, hipMalloc(&s->d_rd_range, (size_t)std::max(ns, 1) * sizeof(int2)));
+    if (n_planes) HIPCHK(s, hipMemcpy(s->d_rd_planes, planes4, (size_t)n_planes * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(s, hipMemcpy(s->d_rd_range, shape_range2, (size_t)ns * sizeof(int2), hipMemcpyHostToDevice));
+    s->rd_nplanes = n_planes;
+    s->rd_planes_set = 1;
+    return 0;
+}
+
+// validate the camera and the env list, grow the scratch, queue the two launches; host_stats != NULL:
+// the tile statistics instead of images (blocks)
+static int render_impl(avr_sim *s, const char *fn, const avr_camera *cam, int32_t n, const int32_t *env_ids, float *d_depth, int32_t *d_id,
+                       uint8_t *d_rgb, int32_t *host_stats) {
+    const int E = s->cfg.n_envs, ns = s->km.ns, nb = s->km.nb;
+    if (!cam) return fail(s, -1, "%s: cam is NULL", fn);
+    if (cam->width < 1 || cam->width > RD_MAX_DIM || cam->height < 1 || cam->height > RD_MAX_DIM)
+        return fail(s, -1, "%s: image %d x %d: width and height must be 1 .. %d", fn, (int)cam->width, (int)cam->height, RD_MAX_DIM);
+    if (!(cam->fov_y_deg > 0.f && cam->fov_y_deg < 180.f)) return fail(s, -1, "%s: fov_y_deg %g outside (0, 180)", fn, (double)cam->fov_y_deg);
+    if (!(cam->near > 0.f) || !(cam->far > cam->near) || !std::isfinite(cam->far))
+        return fail(s, -1, "%s: near %g, far %g: need 0 < near < far", fn, (double)cam->near, (double)cam->far);
+    {
+        double f[3], r[3], nf = 0.0, nu = 0.0, nr = 0.0;
+        for (int q = 0; q < 3; q++) {
+            if (!std::isfinite(cam->eye[q]) || !std::isfinite(cam->target[q]) || !std::isfinite(cam->up[q]))
+                return fail(s, -1, "%s: eye, target or up is not finite", fn);
+            f[q] = (double)cam->target[q] - (double)cam->eye[q];
+            nf += f[q] * f[q];
+            nu += (double)cam->up[q] * cam->up[q];
+        }
+        r[0] = f[1] * cam->up[2] - f[2] * cam->up[1]; r[1] = f[2] * cam->up[0] - f[0] * cam->up[2]; r[2] = f[0] * cam->up[1] - f[1] * cam->up[0];
+        nr = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+        // |f x up| = |f| |up| sin(angle): degenerate below 1e-6 rad, or with a zero vector
+        if (!(nf > 0.0) || !(nu > 0.0) || !(nr > 1e-12 * nf * nu))
+            return fail(s, -1, "%s: degenerate camera: target == eye, or up zero or parallel to the view direction", fn);
+    }
+    if (cam->body < -1 || cam->body >= nb) return fail(s, -1, "%s: camera body %d out of range (-1 .. %d)", fn, (int)cam->body, nb - 1);
+    if (n < 1 || n > 65535) return fail(s, -1, "%s: n = %d envs: must be 1 .. 65535", fn, (int)n);
+    if (!env_ids && n > E) return fail(s, -1, "%s: env_ids NULL selects envs 0 .. n-1, but n = %d > %d envs", fn, (int)n, E);
+    if (env_ids)
+        for (int i = 0; i < n; i++)
+            if (env_ids[i] < 0 || env_ids[i] >= E) return fail(s, -1, "%s: env_ids[%d] = %d out of range (%d envs)", fn, i, (int)env_ids[i], E);
+    if (!host_stats && !d_depth && !d_id && !d_rgb) return fail(s, -1, "%s: d_depth, d_id and d_rgb are all NULL", fn);
+    if (ns < 1 || ns > MAXSH) return fail(s, -1, "%s: %d shapes: the tile lists hold 1 .. %d", fn, ns, MAXSH);
+    if (!s->rd_planes_set)
+        for (int i = 0; i < ns; i++)
+            if (s->h_shape_kind[i] == AVR_HULL)
+                return fail(s, -1, "%s: the scene has convex hulls and no face planes are installed: call avr_render_set_planes first", fn);
+    if (!s->d_rd_range) {       // a scene without hulls: every range is empty
+        HIPCHK(s, hipMalloc(&s->d_rd_range, (size_t)std::max(ns, 1) * sizeof(int2)));
+        HIPCHK(s, hipMemset(s->d_rd_range, 0, (size_t)std::max(ns, 1) * sizeof(int2)));
+        HIPCHK(s, hipMalloc(&s->d_rd_planes, sizeof(float4)));
+    }
+    const int tiles = ((cam->width + RD_TILE - 1) / RD_TILE) * ((cam->height + RD_TILE - 1) / RD_TILE);
+    const size_t need = (size_t)n * (RD_CAM_WORDS + (size_t)RD_REC_WORDS * ns) + (host_stats ? (size_t)2 * n * tiles : 0);
+    if (need > s->rd_scr_cap) {
+        if (s->d_rd_scr) HIPCHK(s, hipFree(s->d_rd_scr));
+        s->d_rd_scr = nullptr;
+        s->rd_scr_cap = 0;
+        HIPCHK(s, hipMalloc(&s->d_rd_scr, need * sizeof(float)));
+        s->rd_scr_cap = need;
+    }
+    if (env_ids && (size_t)n > s->rd_ids_cap) {
+        if (s->d_rd_ids) HIPCHK(s, hipFree(s->d_rd_ids));
+        s->d_rd_ids = nullptr;
+        s->rd_ids_cap = 0;
+        HIPCHK(s, hipMalloc(&s->d_rd_ids, (size_t)n * sizeof(int)));
+        s->rd_ids_cap = (size_t)n;
+    }
+    if (env_ids) HIPCHK(s, hipMemcpyAsync(s->d_rd_ids, env_ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    RdCam c;
+    for (int q = 0; q < 3; q++) { c.eye[q] = cam->eye[q]; c.target[q] = cam->target[q]; c.up[q] = cam->up[q]; }
+    c.th_h = (float)(std::tan(0.5 * (double)cam->fov_y_deg * 3.14159265358979323846 / 180.0) / (double)cam->height);
+    c.near = cam->near; c.far = cam->far;
+    c.W = cam->width; c.H = cam->height; c.body = cam->body;
+    int *d_stats = host_stats ? (int *)(s->d_rd_scr + (size_t)n * (RD_CAM_WORDS + (size_t)RD_REC_WORDS * ns)) : nullptr;
+    HIPCHK(s, avr_launch_render_frames(s->d_km, s->d_state, env_ids ? s->d_rd_ids : nullptr, n, E, c, s->d_rd_hull_radius, s->d_rd_scr, nullptr, s->stream));
+    HIPCHK(s, avr_launch_render_trace(s->d_km, s->d_rd_scr, n, c, s->d_rd_planes, s->d_rd_range, d_depth, d_id, d_rgb, d_stats, s->stream));
+    if (host_stats) {
+        HIPCHK(s, hipMemcpyAsync(host_stats, d_stats, (size_t)2 * n * tiles * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(s, hipStreamSynchronize(s->stream));
+    }
+    return 0;
+}
+
+int avr_render_device(avr_sim *s, const avr_camera *cam, int32_t n, const int32_t *env_ids, float *d_depth, int32_t *d_id, uint8_t *d_rgb) {
+    CHECK_SIM(s);
+    return render_impl(s, "avr_render_device", cam, n, env_ids, d_depth, d_id, d_rgb, nullptr);
+}
+
+int avr_render_tile_stats(avr_sim *s, const avr_camera *cam, int32_t n, const int32_t *env_ids, int32_t *host_stats) {
+    CHECK_SIM(s);
+    if (!host_stats) return fail(s, -1, "avr_render_tile_stats: host_stats is NULL");
+    return render_impl(s, "avr_render_tile_stats", cam, n, env_ids, nullptr, nullptr, nullptr, host_stats);
+}
+
+int avr_render_kernel_info(avr_sim *s, int32_t *out8) {
+    CHECK_SIM(s);
+    if (!out8) return fail(s, -1, "avr_render_kernel_info: out8 is NULL");
+    int o[8];
+    HIPCHK(s, avr_render_attrs(o));
+    for (int i = 0; i < 8; i++) out8[i] = o[i];
     return 0;
 }
 

@@ -1008,6 +1008,23 @@ int avr_get_link_pose(avr_sim *s, int32_t link, float *out7) {
     return fail(s, -1, "avr_get_link_pose: the tool frame is in the state block (AVR_DR_S_TOOL)");
 }
 int avr_get_contact_summary(avr_sim *s, float *out4) { (void)out4; return fail(s, -1, "avr_get_contact_summary: not defined for DressingJaco"); }
+// (the views ray-cast the rigid tasks' collision shapes; the cloth has none)
+#define DRESS_NO_RENDER return fail(s, -1, "render: not built for DressingJaco")
+int32_t avr_n_bodies(avr_sim *s) { DRESS_NO_RENDER; }
+int avr_get_body_poses(avr_sim *s, float *out) { (void)out; DRESS_NO_RENDER; }
+int avr_render_set_planes(avr_sim *s, int32_t n_planes, const float *planes4, const int32_t *shape_range2) {
+    (void)n_planes; (void)planes4; (void)shape_range2;
+    DRESS_NO_RENDER;
+}
+int avr_render_device(avr_sim *s, const avr_camera *cam, int32_t n, const int32_t *env_ids, float *d_depth, int32_t *d_id, uint8_t *d_rgb) {
+    (void)cam; (void)n; (void)env_ids; (void)d_depth; (void)d_id; (void)d_rgb;
+    DRESS_NO_RENDER;
+}
+int avr_render_tile_stats(avr_sim *s, const avr_camera *cam, int32_t n, const int32_t *env_ids, int32_t *host_stats) {
+    (void)cam; (void)n; (void)env_ids; (void)host_stats;
+    DRESS_NO_RENDER;
+}
+int avr_render_kernel_info(avr_sim *s, int32_t *out8) { (void)out8; DRESS_NO_RENDER; }
 int avr_get_flags(avr_sim *s, int32_t *flags) {
     CHECK_SIM(s);
     if (!flags) return fail(s, -1, "avr_get_flags: flags is NULL");

@@ -28,5 +28,6 @@ namespace AVR_NS {
 #include "avr_rollover.hip"
 #include "avr_ppo.hip"
 #include "avr_trainstats.hip"
+#include "avr_render.hip"
 #include "avr_capi.hip"
 }  // namespace AVR_NS

@@ -502,6 +502,88 @@ int avr_get_contact_summary(avr_sim *sim, float *out4);
 int avr_get_flags(avr_sim *sim, int32_t *flags);
 const char *avr_last_error(avr_sim *sim);
 
+/* ---- views of the envs: ray-cast depth, shape ids and RGB (FeedingJaco, ScratchItchPR2, BedBathingPR2;
+ *      DressingJaco: -1) ----
+ * The reference shows its world only through Bullet's GUI (env.py:613-620, record_video_frame :606-608);
+ * p.getCameraImage is the PyBullet call these replace.  csrc/avr_render.hip; new exports only.
+ *
+ * Rendered geometry: the env's collision shapes as its narrowphase addresses them -- the shapes whose
+ * shape_gender is -1 or the gender of the env's proportions slot (T_GENDER), with shape_pose and
+ * shape_param from that slot's row of the per-variant tables (avr_human_variants_set) -- at the body COM
+ * frames the CURRENT state gives: ROBOT links and an articulated human chain by forward kinematics on
+ * S_Q, FREE bodies from S_FREE, HUMAN slots from S_HUMAN, STATIC bodies from st_pose, RSTATIC bodies at
+ * the robot base.  The frames come from the device code with which a sub-step's pair kernel fills its
+ * body-frame table, run on the state as it is now (the table itself is one sub-step old and is not read).
+ *   sphere   shape_param[0] = radius
+ *   capsule  shape_param[0] = radius, [1] = half height, axis along the shape frame's z
+ *   box      shape_param[0..2] = half extents
+ *   hull     the convex hull of its hull_verts (the core, without the 1 mm collision margin), as the face
+ *            planes n . x <= w installed by avr_render_set_planes
+ * A body whose shapes are parked far away (eaten food) is simply out of view.
+ *
+ * Camera: a pinhole with square pixels.  With f = unit(target - eye), right = unit(f x up), upv = right x f,
+ * the ray through the centre of pixel (row r, column c), row 0 at the top, starts at eye along
+ *   d = unit(f + x right + y upv),  x = (2 c + 1 - width) k,  y = (height - 2 r - 1) k,  k = tan(fov_y / 2) / height.
+ * body = -1: eye, target, up are world coordinates; body >= 0: they are given in that collision body's COM
+ * frame of each rendered env (the head slot's body: the participant's view; the tool body: a wrist camera).
+ *
+ * A hit of a ray is a point where it ENTERS a shape (the surface faces the ray) at a parameter t in
+ * [near, far]; a shape that contains the eye, or whose facing surface is nearer than `near`, is not seen.
+ * Outputs per rendered env, row-major [height][width]:
+ *   depth  float32: t of the nearest hit, metres along the unit ray; +inf for a miss
+ *   id     int32: the hit shape's index in the model's shape arrays, -1 for a miss; of two shapes at an
+ *          equal t the lower index wins
+ *   rgb    uint8 [height][width][3]: round_to_nearest(palette[kind] * (0.3 + 0.7 max(0, -n . d))), n the outward
+ *          surface normal at the hit, palette by the hit body's kind: robot and robot-fixed (190, 195, 205),
+ *          free bodies / the tool (240, 200, 60), human (230, 170, 140), static (140, 150, 160); a miss is
+ *          (204, 230, 255), the reference GUI's background (env.py:618).  No textures, visual meshes or shadows.
+ * Nothing is written to the handle's state, workspace or graphs: a render between two steps leaves every
+ * later result bit-identical. */
+typedef struct avr_camera {
+    float eye[3], target[3], up[3];
+    float fov_y_deg;                /* vertical field of view, in (0, 180)                          */
+    float near, far;                /* 0 < near < far: hits outside [near, far] are not seen        */
+    int32_t width, height;          /* 1 .. 4096 each                                               */
+    int32_t body;                   /* -1: world frame; else a collision body index                 */
+    int32_t reserved[3];            /* 0                                                            */
+} avr_camera;
+/* Collision bodies of the handle's scene. */
+int32_t avr_n_bodies(avr_sim *sim);
+/* avr_get_body_poses: the world COM frame (x y z, qx qy qz qw) of every collision body of every env as
+ *   defined above, out[n_envs][avr_n_bodies][7] on the host (blocks until done): the counterpart of
+ *   p.getBasePositionAndOrientation / p.getLinkState for all bodies at once, and what the renderer
+ *   places the shapes at. */
+int avr_get_body_poses(avr_sim *sim, float *out);
+/* avr_render_set_planes: install the hulls' face planes: planes4[n_planes][4] = (n, w) with unit n in the
+ *   shape's frame, shape_range2[n_shapes][2] = (first plane, plane count) per shape, count 0 for shapes
+ *   that are no hull and >= 4 for every hull (host arrays; avr/render.py hull_planes builds them from
+ *   hull_verts).  The planes belong to the base hulls; height variants move and scale shapes through
+ *   shape_pose / shape_param only.  A later call replaces the set (the call waits for the stream). */
+int avr_render_set_planes(avr_sim *sim, int32_t n_planes, const float *planes4, const int32_t *shape_range2);
+/* avr_render_device: render the n envs env_ids[0 .. n-1] (a host array, validated and copied in; NULL: envs
+ *   0 .. n-1; repeats allowed, the order is the output order) through *cam into the device buffers
+ *   d_depth[n][height][width], d_id[n][height][width], d_rgb[n][height][width][3]; any of the three may be
+ *   NULL, not all.  Queued on avr_stream(sim); the call does not wait for the images.  Two things can
+ *   make the host wait all the same: a call that needs more scratch than any before it (more envs or more
+ *   shapes) frees and reallocates it, which waits for the device, and the copy of a non-NULL env_ids reads
+ *   the caller's pageable array, which the runtime may finish before it returns (the array is free to
+ *   change once the call is back).  env_ids NULL and a steady n have neither.
+ *   Errors (-1, message in avr_last_error, nothing launched): cam NULL; width or height < 1 or > 4096;
+ *   fov_y_deg outside (0, 180); near <= 0 or far <= near; a degenerate view (target == eye, up zero or
+ *   parallel to the view direction) or a non-finite field; n < 1 or n > 65535; an env id outside
+ *   0 .. n_envs-1; body outside -1 .. avr_n_bodies-1; all three outputs NULL; a scene with hulls before
+ *   avr_render_set_planes. */
+int avr_render_device(avr_sim *sim, const avr_camera *cam, int32_t n, const int32_t *env_ids, float *d_depth, int32_t *d_id, uint8_t *d_rgb);
+/* Diagnostics of the renderer (no reference counterpart; tools/render_bench.py reads them, nothing else
+ * needs them).
+ * avr_render_tile_stats: what the tile culling of avr_render_device leaves for the same
+ *   arguments: host_stats[n][tiles][2] = {shapes in the tile's culled list, hull planes a pixel of the tile
+ *   tests}, tiles = ceil(width / 8) * ceil(height / 8), row-major over the tile grid (blocks until done).  It
+ *   runs both launches of a render with no image written.
+ * avr_render_kernel_info: out8 = [vgprs, 0, lds_bytes, scratch_bytes] of the frame and the trace kernel. */
+int avr_render_tile_stats(avr_sim *sim, const avr_camera *cam, int32_t n, const int32_t *env_ids, int32_t *host_stats);
+int avr_render_kernel_info(avr_sim *sim, int32_t *out8);
+
 /* ---- device reset (FeedingJaco) ----
  * avr_reset_ik: avr_reset with the reset's inverse kinematics on the device.  Replaces the IK of
  *   FeedingEnv.reset (feeding.py:276-278 -> util.py:34-105 ik_random_restarts) for the masked envs:
