@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get('AVR_LIB') or os.path.join(HERE, 'libavr.so')   # AVR_
 EXPORTS = [
     'avr_create', 'avr_destroy', 'avr_set_state', 'avr_get_state', 'avr_set_state_masked', 'avr_settle',
     'avr_step', 'avr_step_device', 'avr_step_random_device', 'avr_rollout_random_device', 'avr_random_actions_device', 'avr_sync',
-    'avr_stream', 'avr_state_device_ptr', 'avr_n_envs', 'avr_env_groups', 'avr_dyn_split', 'avr_pairs_flat', 'avr_np_hot', 'avr_state_words', 'avr_abi_version',
+    'avr_stream', 'avr_state_device_ptr', 'avr_n_envs', 'avr_env_groups', 'avr_dyn_split', 'avr_pairs_flat', 'avr_np_hot', 'avr_coop_wsup', 'avr_state_words', 'avr_abi_version',
     'avr_kernel_info', 'avr_last_error', 'avr_substep', 'avr_reset', 'avr_profile_kernels', 'avr_kernel_times',
     'avr_hull_support_table', 'avr_task', 'avr_task_state_words', 'avr_task_obs_dim', 'avr_task_act_dim', 'avr_n_dof',
     'avr_get_q', 'avr_get_link_pose', 'avr_get_contact_summary', 'avr_get_flags', 'avr_reset_ik', 'avr_base_search',
@@ -182,6 +182,8 @@ def load(path=LIB_PATH):
     lib.avr_pairs_flat.restype = C.c_int32
     lib.avr_np_hot.argtypes = [vp]
     lib.avr_np_hot.restype = C.c_int32
+    lib.avr_coop_wsup.argtypes = [vp]
+    lib.avr_coop_wsup.restype = C.c_int32
     lib.avr_graph_captures.argtypes = [vp]
     lib.avr_graph_captures.restype = C.c_int64
     lib.avr_state_words.restype = C.c_int32
@@ -613,6 +615,10 @@ class Sim:
     def np_hot(self):
         """1 when the narrowphase starts the contact pool's sphere-hull pairs first (AVR_NP_HOT, per-task default)."""
         return int(self.lib.avr_np_hot(self.h))
+
+    def coop_wsup(self):
+        """1 when the cooperative narrowphase takes hull supports wave-wide (AVR_COOP_WSUP, per-task default)."""
+        return int(self.lib.avr_coop_wsup(self.h))
 
     def graph_captures(self):
         """HIP-graph captures this handle has made (one per distinct output-buffer key)."""

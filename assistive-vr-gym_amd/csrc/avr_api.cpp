@@ -23,6 +23,7 @@
     int32_t avr_dyn_split(const avr_sim *s);                                                                       \
     int32_t avr_pairs_flat(const avr_sim *s);                                                                      \
     int32_t avr_np_hot(const avr_sim *s);                                                                          \
+    int32_t avr_coop_wsup(const avr_sim *s);                                                                       \
     int64_t avr_graph_captures(avr_sim *s);                                                                        \
     int32_t avr_n_dof(avr_sim *s);                                                                                 \
     int avr_set_state(avr_sim *s, const float *h);                                                                 \
@@ -222,6 +223,7 @@ int32_t avr_env_groups(avr_sim *s) { if (!s || !s->impl) return 0; DISPATCH(s, a
 int32_t avr_dyn_split(const avr_sim *s) { if (!s || !s->impl) return 0; DISPATCH(s, avr_dyn_split(h)); }
 int32_t avr_pairs_flat(const avr_sim *s) { if (!s || !s->impl) return 0; DISPATCH(s, avr_pairs_flat(h)); }
 int32_t avr_np_hot(const avr_sim *s) { if (!s || !s->impl) return 0; DISPATCH(s, avr_np_hot(h)); }
+int32_t avr_coop_wsup(const avr_sim *s) { if (!s || !s->impl) return 0; DISPATCH(s, avr_coop_wsup(h)); }
 int32_t avr_n_dof(avr_sim *s) { if (!s || !s->impl) return 0; DISPATCH(s, avr_n_dof(h)); }
 int64_t avr_graph_captures(avr_sim *s) { if (!s || !s->impl) return -1; DISPATCH(s, avr_graph_captures(h)); }
 int avr_set_state(avr_sim *s, const float *p) { DISPATCH(s, avr_set_state(h, p)); }

@@ -558,6 +558,11 @@ int avr_create(const avr_config *cfg, const avr_model_desc *d, avr_sim **out) {
     k.np_hot = K_NP_HOT;
     if (const char *nh = getenv("AVR_NP_HOT"))
         if ((nh[0] == '0' || nh[0] == '1') && !nh[1]) k.np_hot = nh[0] == '1';
+    // wave-wide hull supports on the cooperative narrowphase path (K_COOP_WSUP: the task's default); AVR_COOP_WSUP=0|1
+    // overrides (the same support vertex either way: the same bits)
+    k.coop_wsup = K_COOP_WSUP;
+    if (const char *cw = getenv("AVR_COOP_WSUP"))
+        if ((cw[0] == '0' || cw[0] == '1') && !cw[1]) k.coop_wsup = cw[0] == '1';
     if (E * (size_t)k.rowstride * sizeof(float) >= 0x7fff0000ull) {
         int r = fail(s, -2, "n_envs %d exceeds the row-buffer addressing limit (%d per handle)", cfg->n_envs, (int)(0x7fff0000ull / (k.rowstride * sizeof(float))));
         return r;
@@ -752,6 +757,7 @@ int32_t avr_env_groups(avr_sim *s) { return s ? s->ngroups : 0; }
 int32_t avr_dyn_split(const avr_sim *s) { return s ? s->km.dyn_split : 0; }
 int32_t avr_pairs_flat(const avr_sim *s) { return s ? s->km.pairs_flat : 0; }
 int32_t avr_np_hot(const avr_sim *s) { return s ? s->km.np_hot : 0; }
+int32_t avr_coop_wsup(const avr_sim *s) { return s ? s->km.coop_wsup : 0; }
 
 #define CHECK_SIM(s)                         \
     if (!(s) || !(s)->d_state) return -1;    \

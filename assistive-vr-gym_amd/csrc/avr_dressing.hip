@@ -755,6 +755,7 @@ int32_t avr_env_groups(avr_sim *s) { return s ? 1 : 0; }
 int32_t avr_dyn_split(const avr_sim *) { return 0; }
 int32_t avr_pairs_flat(const avr_sim *) { return 0; }
 int32_t avr_np_hot(const avr_sim *) { return 0; }
+int32_t avr_coop_wsup(const avr_sim *) { return 0; }
 int32_t avr_n_dof(avr_sim *s) { return s ? 7 : 0; }
 int64_t avr_graph_captures(avr_sim *s) { return s ? 0 : -1; }
 

@@ -133,7 +133,7 @@ AVR_DI BBForces bb_forces(const KModel &m, EnvLDS &L, BBShared &B, const float *
 #define WS_BB_CAP (WS_WORDS - WS_BB_PAIRS)
 static_assert(WS_FW + 4 * MAXF <= WS_BB_N, "the stalled-pair queue lies past the velocity words");
 struct BBView { const float *st; int gender; };
-template <bool OVF = false, class LT>
+template <bool OVF = false, int WSM = 2, class LT>
 AVR_DI float bb_closest(const KModel &m, const LT &L, EpaBuf &E, float *ws, int &ns, const int cap = WS_BB_CAP) {
     const int lane = lane_id();
     const int vso = lvrow(L, m) * m.ns;     // the human's shapes: the env's variant's
@@ -193,7 +193,7 @@ AVR_DI float bb_closest(const KModel &m, const LT &L, EpaBuf &E, float *ws, int 
             v3 nB = V(0, 0, 0), pB = V(0, 0, 0);
             float d = 0.f;
             int nit, nk;
-            const int rc = narrowphase<true>(m, E, A, Bs, thr, nB, pB, d, nit, nk, nullptr, OVF);
+            const int rc = narrowphase<true, WSM>(m, E, A, Bs, thr, nB, pB, d, nit, nk, nullptr, OVF);
             SYNC();
             if (lane == 0 && rc == 1) dmin = fminf(dmin, d);
         }
@@ -211,6 +211,7 @@ AVR_DI float bb_reward(const KModel &m, float dmin, float asq, float wiped, floa
 
 // Task glue after the frames (BedBathingEnv.step after take_step, bed_bathing.py:54-75); SETTLE
 // mode: the reset observation (_get_obs([0], [0, 0]), :351).  NaN guard for every mode.
+template <int WSM>
 __global__ __launch_bounds__(64) void avr_task_kernel(const KModel *__restrict__ mp, float *__restrict__ state, float *__restrict__ obs,
                                                       float *__restrict__ rew, unsigned char *__restrict__ done, float *__restrict__ info,
                                                       const unsigned char *__restrict__ mask, int mode, int env0, int n_envs) {
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(64) void avr_task_kernel(const KModel *__restrict__
         const BBForces F = bb_forces(m, L, B, gcp, env_cs(m, env) + CS_BTF);
         float *ws = env_ws(m, env);
         int nq;
-        const float dmin = bb_closest(m, L, E, ws, nq);
+        const float dmin = bb_closest<false, WSM>(m, L, E, ws, nq);
         const tf tb = ldtf(L.st + S_FREE);
         const v3 tip = qrot(tb.q, V(m.tool_tip[0], m.tool_tip[1], m.tool_tip[2]));
         // tool link 1's linear velocity (getLinkState(tool, 1, computeLinkVelocity=True)[6], :55)
@@ -276,6 +277,7 @@ __global__ __launch_bounds__(64) void avr_task_kernel(const KModel *__restrict__
 // the minimum over them and the other pairs' minimum (WS_BB_DMIN).  ns: the env's stalled pairs
 // (WS_BB_N); with more of them than the queue's capacity the lane GJK of every pair runs again to
 // find the others (bb_closest<true>).  Wave-cooperative.
+template <int WSM = 2>
 AVR_DI float bb_stall_min(const KModel &m, EpaBuf &E, const float *gst, float *ws, int ns, const int cap = WS_BB_CAP) {
     const int nq = min(ns, cap);
     const tf ttf = ldtf(gst + S_FREE);
@@ -290,19 +292,20 @@ AVR_DI float bb_stall_min(const KModel &m, EpaBuf &E, const float *gst, float *w
         v3 nB = V(0, 0, 0), pB = V(0, 0, 0);
         float d = 0.f;
         int nit, nk;
-        const int rc = narrowphase<true>(m, E, A, Bs, thr, nB, pB, d, nit, nk, nullptr, true);
+        const int rc = narrowphase<true, WSM>(m, E, A, Bs, thr, nB, pB, d, nit, nk, nullptr, true);
         SYNC();
         if (rc == 1) dmin = fminf(dmin, d);
     }
     if (ns > cap) {
         int n2;
-        dmin = fminf(dmin, bb_closest<true>(m, BBView{gst, slot_gender(m, slot)}, E, ws, n2, cap));
+        dmin = fminf(dmin, bb_closest<true, WSM>(m, BBView{gst, slot_gender(m, slot)}, E, ws, n2, cap));
     }
     return dmin;
 }
 
 // The step's stalled pairs: the reward finished from the full minimum (bb_reward).  One wave per
 // env; an env with an empty queue (nearly all) returns at once.
+template <int WSM>
 __global__ __launch_bounds__(64) void avr_bb_stall_kernel(const KModel *__restrict__ mp, float *__restrict__ state, float *__restrict__ rew,
                                                           const unsigned char *__restrict__ mask, int env0, int n_envs) {
     __shared__ EpaBuf E;
@@ -312,7 +315,7 @@ __global__ __launch_bounds__(64) void avr_bb_stall_kernel(const KModel *__restri
     float *ws = env_ws(m, env);
     const int ns = __float_as_int(ws[WS_BB_N]);
     if (ns <= 0) return;
-    const float dmin = bb_stall_min(m, E, state + (size_t)env * K_STATE_WORDS, ws, ns);
+    const float dmin = bb_stall_min<WSM>(m, E, state + (size_t)env * K_STATE_WORDS, ws, ns);
     if (lane_id() == 0) rew[env] = bb_reward(m, dmin, ws[WS_ASQ], ws[WS_BB_WIPED], ws[WS_BB_PREFS]);
 }
 

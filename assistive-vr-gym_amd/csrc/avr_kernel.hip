@@ -750,6 +750,7 @@ AVR_DI v3 support(const KModel &m, const WShape &s, v3 d) {
                 if (dd > best) { best = dd; bi = i; }
             }
             bi = wave_argmax(best, bi);
+            if (bi == 0x7fffffff) bi = 0;     // no lane found a product above -BIGF (a NaN direction): vertex 0
             const float4 v = hv[bi];
             r = V(v.x, v.y, v.z);
         } else {
@@ -820,6 +821,145 @@ AVR_DI void support2(const KModel &m, const WShape &A, v3 da, const WShape &B, v
     }
     ra = tfpt(A.t, V(bva.x, bva.y, bva.z));
     rb = tfpt(B.t, V(bvb.x, bvb.y, bvb.z));
+}
+
+// Wave-wide supports of a cooperative pair (KModel.coop_wsup; the whole wave works on one pair).
+// A hull of at most 64 vertices is resident: lane i holds its local vertex i (a: shape A's, b:
+// shape B's), loaded once when the pair starts, and a query costs no memory access -- one product
+// per lane, wave_argmax, a lane read of the winner.  A larger table hull reads its cell's
+// candidates one per lane: two dependent round trips whatever the cell holds.  Both return the
+// vertex the serial scans return: the first strictly largest projection in vertex (candidate)
+// order is wave_argmax's lowest index among the largest, and the table's candidates hold the
+// hull's (avr_hulltab.cpp).
+struct WRes {
+    v3 a, b;
+    bool on, ra, rb;        // the switch; A / B resident
+};
+#ifdef AVR_PROF
+// the running cooperative pair's support queries (np_coop reads them): cycles inside them, their
+// number, the most candidates a table cell held (wave-wide path only)
+__shared__ unsigned long long wsup_prof[3];
+#endif
+
+// WSM: 0 the serial scans only (the wave-wide code is compiled out: the kernel is what it was
+// without the switch), 1 wave-wide only, 2 KModel.coop_wsup read here.  The step's kernels come in
+// instances 0 and 1 and the launch picks one; the test hooks and the reset kernels take 2
+template <int WSM>
+AVR_DI WRes make_wres(const KModel &m, const WShape &A, const WShape &B) {
+    WRes R;
+    R.on = WSM == 1 || (WSM == 2 && m.coop_wsup != 0);
+    R.ra = R.on && A.kind == AVR_HULL && A.nv >= 1 && A.nv <= 64;
+    R.rb = R.on && B.kind == AVR_HULL && B.nv >= 1 && B.nv <= 64;
+    float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
+    if (R.ra) va = GlobalF4{m.hull_verts + A.vs}[min(lane_id(), A.nv - 1)];     // (lanes past nv hold a copy of the last vertex)
+    if (R.rb) vb = GlobalF4{m.hull_verts + B.vs}[min(lane_id(), B.nv - 1)];
+    R.a = V(va.x, va.y, va.z);
+    R.b = V(vb.x, vb.y, vb.z);
+    return R;
+}
+
+// the winner among the lanes with `in` set: the lowest index idx of the largest dd; a product that
+// is not above -BIGF (NaN) never wins, and with no winner at all the answer is 0x7fffffff
+AVR_DI int wsup_pick(float dd, int idx, bool in) {
+    const bool ok = in && dd > -BIGF;
+    return __builtin_amdgcn_readfirstlane(wave_argmax(ok ? dd : -BIGF, ok ? idx : 0x7fffffff));
+}
+
+// local support vertex of a resident hull (lane i: vertex i = v) for the local direction l; a zero
+// or NaN direction keeps vertex 0, as the serial scans do.  (One unreachable difference: a direction
+// with a NaN component and mx > 0 -- qrot spreads a NaN over all three -- finds no winner; this keeps
+// vertex 0, the serial table scan its cell's first candidate.  The results are NaN either way.)
+AVR_DI v3 support_res(v3 v, int nv, v3 l, float mx) {
+    int w = 0;
+    if (mx > 0.f) {
+        const float dd = l.x * v.x + l.y * v.y + l.z * v.z;
+        w = wsup_pick(dd, lane_id(), lane_id() < nv);
+        if (w == 0x7fffffff) w = 0;
+    }
+    return V(rdl_f(v.x, w), rdl_f(v.y, w), rdl_f(v.z, w));
+}
+
+// local support point of a side that is neither resident nor scanning a table cell: support()'s
+// spheres, capsules and boxes; a table hull comes here only with a zero / NaN direction and keeps
+// vertex 0; a big hull without a table by the whole wave's scan (the first strictly largest
+// projection, vertex 0 where no product is above -BIGF), as support<true> has it
+AVR_DI v3 support_rest(const KModel &m, const WShape &s, v3 l) {
+    if (s.kind == AVR_SPHERE) return V(0, 0, 0);
+    if (s.kind == AVR_CAPSULE) return V(0, 0, l.z >= 0.f ? s.he.y : -s.he.y);
+    if (s.kind == AVR_BOX) return V(l.x >= 0.f ? s.he.x : -s.he.x, l.y >= 0.f ? s.he.y : -s.he.y, l.z >= 0.f ? s.he.z : -s.he.z);
+    const GlobalF4 hv{m.hull_verts + s.vs};
+    float best = -BIGF;
+    int bi = 0x7fffffff;
+    for (int i = lane_id(); i < (s.tab >= 0 ? 0 : s.nv); i += 64) {
+        const float4 v = hv[i];
+        const float dd = l.x * v.x + l.y * v.y + l.z * v.z;
+        if (dd > best) { best = dd; bi = i; }
+    }
+    bi = wave_argmax(best, bi);
+    if (bi == 0x7fffffff) bi = 0;
+    const float4 v = hv[bi];
+    return V(v.x, v.y, v.z);
+}
+
+// support2() with the hulls' supports taken wave-wide (R.on; every lane passes the same arguments)
+AVR_DI void support2w(const KModel &m, const WShape &A, v3 da, const WShape &B, v3 db, const WRes &R, v3 &ra, v3 &rb) {
+    const int lane = lane_id();
+    const v3 la = qrot(qconj(A.t.q), da), lb = qrot(qconj(B.t.q), db);
+    const float mxa = fmaxf(fabsf(la.x), fmaxf(fabsf(la.y), fabsf(la.z))), mxb = fmaxf(fabsf(lb.x), fmaxf(fabsf(lb.y), fabsf(lb.z)));
+    // the sides that scan a table cell: the two cell lookups, then the candidates, side by side
+    const bool ta = A.kind == AVR_HULL && !R.ra && A.tab >= 0 && mxa > 0.f, tb = B.kind == AVR_HULL && !R.rb && B.tab >= 0 && mxb > 0.f;
+    if (ta || tb) {
+        const GlobalF4 tv{m.tab_vert};
+        int2 ca = make_int2(0, 0), cb = make_int2(0, 0);
+        if (ta) ca = tab_cell_of(m, A.tab, la, mxa);
+        if (tb) cb = tab_cell_of(m, B.tab, lb, mxb);
+#ifdef AVR_PROF
+        if (lane == 0) wsup_prof[2] = max(wsup_prof[2], (unsigned long long)max(ca.y, cb.y));
+#endif
+        // lane q takes candidates q, q + 64, ... and keeps its own first strictly largest; the
+        // cell's first candidate stands in where nothing wins (the serial scan's initial value)
+        float besta = -BIGF, bestb = -BIGF;
+        int bia = 0x7fffffff, bib = 0x7fffffff;
+        float4 bva = make_float4(0.f, 0.f, 0.f, 0.f), bvb = bva;
+        const int n = max(1, max(ca.y, cb.y));
+        for (int k0 = 0; k0 < n; k0 += 64) {
+            const int k = k0 + lane;
+            const bool ina = ta && k < ca.y, inb = tb && k < cb.y;
+            float4 va = bva, vb = bvb;
+            if (ina || (ta && k == 0)) va = tv[ca.x + k];
+            if (inb || (tb && k == 0)) vb = tv[cb.x + k];
+            if (k == 0) { bva = va; bvb = vb; }
+            const float d1 = la.x * va.x + la.y * va.y + la.z * va.z;
+            if (ina && d1 > besta) { besta = d1; bia = k; bva = va; }
+            const float d2 = lb.x * vb.x + lb.y * vb.y + lb.z * vb.z;
+            if (inb && d2 > bestb) { bestb = d2; bib = k; bvb = vb; }
+        }
+        if (ta) {
+            int w = wsup_pick(besta, bia, true);
+            w = w == 0x7fffffff ? 0 : w & 63;        // (candidate k lives in lane k % 64)
+            ra = tfpt(A.t, V(rdl_f(bva.x, w), rdl_f(bva.y, w), rdl_f(bva.z, w)));
+        }
+        if (tb) {
+            int w = wsup_pick(bestb, bib, true);
+            w = w == 0x7fffffff ? 0 : w & 63;
+            rb = tfpt(B.t, V(rdl_f(bvb.x, w), rdl_f(bvb.y, w), rdl_f(bvb.z, w)));
+        }
+    }
+    // the other sides: a resident hull from registers, the rest as support() has them
+    if (!ta) ra = tfpt(A.t, R.ra ? support_res(R.a, A.nv, la, mxa) : support_rest(m, A, la));
+    if (!tb) rb = tfpt(B.t, R.rb ? support_res(R.b, B.nv, lb, mxb) : support_rest(m, B, lb));
+}
+
+// the cooperative path's support pair, through the switch
+AVR_DI void support2c(const KModel &m, const WShape &A, v3 da, const WShape &B, v3 db, const WRes &R, v3 &ra, v3 &rb) {
+#ifdef AVR_PROF
+    const unsigned long long t0 = __builtin_readcyclecounter();
+#endif
+    if (R.on) support2w(m, A, da, B, db, R, ra, rb);
+    else support2<true>(m, A, da, B, db, ra, rb);
+#ifdef AVR_PROF
+    if (lane_id() == 0) { wsup_prof[0] += __builtin_readcyclecounter() - t0; wsup_prof[1]++; }
+#endif
 }
 
 // --------------------------------------------------------------------------- GJK
@@ -1094,7 +1234,7 @@ AVR_DI int simplex_closest_d(Simplex &S, v3 &vout, float lam[4]) {
 #ifndef GJK_NB
 #define GJK_NB 4
 #endif
-AVR_DI int gjk_coop_d(const KModel &m, const WShape &A, const WShape &B, float maxdist2, v3 &pa, v3 &pb, float &dist, Simplex &S, int &nit) {
+AVR_DI int gjk_coop_d(const KModel &m, const WShape &A, const WShape &B, const WRes &R, float maxdist2, v3 &pa, v3 &pb, float &dist, Simplex &S, int &nit) {
     v3 v = sub(A.t.p, B.t.p);
     if (len2(v) < 1e-20f) v = V(1, 0, 0);
     S.n = 0;
@@ -1104,7 +1244,7 @@ AVR_DI int gjk_coop_d(const KModel &m, const WShape &A, const WShape &B, float m
     for (int it = 0; it < GJK_MAX_IT; it++) {
         nit = it + 1;
         v3 sa, sb;
-        support2<true>(m, A, scl(v, -1.f), B, v, sa, sb);
+        support2c(m, A, scl(v, -1.f), B, v, R, sa, sb);
         v3 wv = sub(sa, sb);
         float vv = len2(v), vw = dot(v, wv);
         if (vw > 0.f && vw * vw > vv * maxdist2) return GJK_FAR;
@@ -1138,7 +1278,7 @@ AVR_DI int gjk_coop_d(const KModel &m, const WShape &A, const WShape &B, float m
 
 // the cooperative GJK in fp32 (pairs the lane path hands over for EPA or a big hull): the lane
 // path's arithmetic with both supports of an iteration issued together
-AVR_DI int gjk_coop_f(const KModel &m, const WShape &A, const WShape &B, float maxdist2, v3 &pa, v3 &pb, float &dist, Simplex &S, int &nit) {
+AVR_DI int gjk_coop_f(const KModel &m, const WShape &A, const WShape &B, const WRes &R, float maxdist2, v3 &pa, v3 &pb, float &dist, Simplex &S, int &nit) {
     v3 v = sub(A.t.p, B.t.p);
     if (len2(v) < 1e-20f) v = V(1, 0, 0);
     S.n = 0;
@@ -1148,7 +1288,7 @@ AVR_DI int gjk_coop_f(const KModel &m, const WShape &A, const WShape &B, float m
     for (int it = 0; it < GJK_MAX_IT; it++) {
         nit = it + 1;
         v3 sa, sb;
-        support2<true>(m, A, scl(v, -1.f), B, v, sa, sb);
+        support2c(m, A, scl(v, -1.f), B, v, R, sa, sb);
         v3 wv = sub(sa, sb);
         float vv = len2(v), vw = dot(v, wv);
         if (vw > 0.f && vw * vw > vv * maxdist2) return GJK_FAR;
@@ -1238,8 +1378,8 @@ AVR_DI int gjk_lane(const KModel &m, const WShape &A, const WShape &B, float max
 }
 
 template <bool COOP>
-AVR_DI int gjk(const KModel &m, const WShape &A, const WShape &B, float maxdist2, v3 &pa, v3 &pb, float &dist, Simplex &S, int &nit, bool dbl) {
-    if constexpr (COOP) return dbl ? gjk_coop_d(m, A, B, maxdist2, pa, pb, dist, S, nit) : gjk_coop_f(m, A, B, maxdist2, pa, pb, dist, S, nit);
+AVR_DI int gjk(const KModel &m, const WShape &A, const WShape &B, const WRes &R, float maxdist2, v3 &pa, v3 &pb, float &dist, Simplex &S, int &nit, bool dbl) {
+    if constexpr (COOP) return dbl ? gjk_coop_d(m, A, B, R, maxdist2, pa, pb, dist, S, nit) : gjk_coop_f(m, A, B, R, maxdist2, pa, pb, dist, S, nit);
     else return gjk_lane(m, A, B, maxdist2, pa, pb, dist, S, nit);
 }
 
@@ -1276,7 +1416,7 @@ AVR_DI void epa_set_vert(EpaBuf &L, int vi, v3 w, v3 a, v3 b) {
     SYNC();
 }
 
-AVR_DI int epa(const KModel &m, EpaBuf &L, const WShape &A, const WShape &B, const Simplex &S, v3 &normal_out, float &depth, v3 &pa, v3 &pb) {
+AVR_DI int epa(const KModel &m, EpaBuf &L, const WShape &A, const WShape &B, const WRes &R, const Simplex &S, v3 &normal_out, float &depth, v3 &pa, v3 &pb) {
     int nv = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++)
@@ -1296,7 +1436,7 @@ AVR_DI int epa(const KModel &m, EpaBuf &L, const WShape &A, const WShape &B, con
             if (len2(d) < 1e-24f) continue;
         }
         v3 sa, sb;
-        support2<true>(m, A, d, B, scl(d, -1.f), sa, sb);
+        support2c(m, A, d, B, scl(d, -1.f), R, sa, sb);
         v3 wv = sub(sa, sb);
         bool dup = false;
         for (int k = 0; k < nv; k++)
@@ -1335,7 +1475,7 @@ AVR_DI int epa(const KModel &m, EpaBuf &L, const WShape &A, const WShape &B, con
         if (best < 0) return -1;
         v3 n = ld3(L.eFn[best]);
         v3 sa, sb;
-        support2<true>(m, A, n, B, scl(n, -1.f), sa, sb);
+        support2c(m, A, n, B, scl(n, -1.f), R, sa, sb);
         v3 wv = sub(sa, sb);
         float dist = dot(wv, n);
         if (dist - L.eFn[best][3] < EPA_EPS || nv >= EPA_MAX_V) break;
@@ -1446,7 +1586,7 @@ AVR_DI int epa(const KModel &m, EpaBuf &L, const WShape &A, const WShape &B, con
 // returns: 0 no contact, 1 contact (nB, pB, dist), 2 needs the cooperative path
 // (nit, kind: diagnostic out-parameters -- GJK iterations, and 0 sphere-sphere, 1 sphere-box,
 // 2 sphere-capsule, 3 GJK; unused outside the AVR_PROF build)
-template <bool COOP>
+template <bool COOP, int WSM = 2>
 AVR_DI int narrowphase(const KModel &m, EpaBuf &E, const WShape &A, const WShape &B, float thr, v3 &nB, v3 &pB, float &dist, int &nit, int &kind,
                        int *epa_budget = nullptr, bool dbl = false) {
     int ka = A.kind, kb = B.kind;
@@ -1521,7 +1661,11 @@ AVR_DI int narrowphase(const KModel &m, EpaBuf &E, const WShape &A, const WShape
     v3 pa, pb;
     float cd;
     Simplex S;
-    int st = gjk<COOP>(m, A, B, maxd * maxd, pa, pb, cd, S, nit, dbl);
+    // a cooperative pair's resident hull vertices (KModel.coop_wsup), loaded once for all its support queries
+    WRes R;
+    if constexpr (COOP) R = make_wres<WSM>(m, A, B);
+    else R.on = R.ra = R.rb = false;
+    int st = gjk<COOP>(m, A, B, R, maxd * maxd, pa, pb, cd, S, nit, dbl);
     if (st == GJK_FAR) return 0;
     if (st == GJK_UNFINISHED) return 2;
     if (st == GJK_STALLED) return 4;
@@ -1538,7 +1682,7 @@ AVR_DI int narrowphase(const KModel &m, EpaBuf &E, const WShape &A, const WShape
         }
         float depth;
         v3 en;
-        if (epa(m, E, A, B, S, en, depth, pa, pb)) return 0;
+        if (epa(m, E, A, B, R, S, en, depth, pa, pb)) return 0;
         n = scl(en, -1.f);
         d = -depth - ma - mb;
     }
@@ -3592,6 +3736,7 @@ AVR_DI void np_store(float *cs, int k, int rc, v3 nB, v3 pB, float d) {
 #ifndef AVR_COOP_PERSIST
 #define AVR_COOP_PERSIST 20
 #endif
+template <int WSM>
 AVR_DI int np_coop(const KModel &m, float *cs, int n, EpaBuf &E, int rot, int budget) {
     const int lane = lane_id();
     const int vrow = cs_vrow(m, cs), vbo = vrow * m.nb, vso = vrow * m.ns;
@@ -3630,9 +3775,11 @@ AVR_DI int np_coop(const KModel &m, float *cs, int n, EpaBuf &E, int rot, int bu
                 float d2 = 0.f;
                 int nit, nk;
 #ifdef AVR_PROF
+                if (lane == 0) wsup_prof[0] = wsup_prof[1] = wsup_prof[2] = 0;
+                SYNC();
                 const unsigned long long c0t = __builtin_readcyclecounter();
 #endif
-                int r2 = narrowphase<true>(m, E, A, B, thr, n2, p2, d2, nit, nk, &budget, (bd[q] >> j) & 1ull);
+                int r2 = narrowphase<true, WSM>(m, E, A, B, thr, n2, p2, d2, nit, nk, &budget, (bd[q] >> j) & 1ull);
                 if (r2 == 3) { r2 = 0; skipped++; }
 #ifdef AVR_PROF
                 if (m.prof && lane == 0) {     // cooperative pairs, their GJK iterations, the time they took
@@ -3648,6 +3795,12 @@ AVR_DI int np_coop(const KModel &m, float *cs, int n, EpaBuf &E, int rot, int bu
                     if ((A.nv > SMALL_NV && A.tab < 0) || (B.nv > SMALL_NV && B.tab < 0)) atomicAdd(pr + 22, 1ull);
                     atomicAdd(pr + 29, dc);
                     atomicMax(pr + 30, dc);
+                    // support queries: 23 cycles inside them, 31 their number; 47 the env's slowest pair, packed:
+                    // cycles << 36 | support cycles << 12 | queries (tools/coop_support_prof.py)
+                    atomicAdd(pr + 23, wsup_prof[0]);
+                    atomicAdd(pr + 31, wsup_prof[1]);
+                    atomicMax(pr + 47, dc << 36 | (wsup_prof[0] & 0xffffffull) << 12 | (wsup_prof[1] & 0xfffull));
+                    atomicMax(pr + 5, wsup_prof[2]);
                 }
 #endif
                 SYNC();
@@ -3939,7 +4092,7 @@ __global__ __launch_bounds__(64) void avr_coop_kernel(const KModel *__restrict__
     if (gld(env_cs(m, env) + CS_COOP) != 0.f) {
         float *ws = env_ws(m, env);
         const int rot = __float_as_int(gld(ws + WS_COOPROT));
-        (void)np_coop(m, env_cs(m, env), __float_as_int(gld(env_cs(m, env) + CS_NSP)), E, rot, 1 << 30);
+        (void)np_coop<2>(m, env_cs(m, env), __float_as_int(gld(env_cs(m, env) + CS_NSP)), E, rot, 1 << 30);
         if (lane_id() == 0) ws[WS_COOPROT] = __int_as_float(rot + AVR_COOP_CAP);
     }
 }
@@ -3951,6 +4104,7 @@ __global__ __launch_bounds__(64) void avr_coop_kernel(const KModel *__restrict__
 // non-contact rows, or (dynamics split) the load of what the pair launch's dynamics role left.  The cooperative pairs open this
 // kernel rather than a kernel of their own: the few envs that have one (an EPA can take ~40 us)
 // delay only their own wave, not a whole launch that every env's kernel a waits behind.
+template <int WSM>
 AVR_DI void substep_a_env(const KModel &m, EnvLDS &L, float *__restrict__ state, float dt, int env, int n_envs) {
     (void)n_envs;
     WT_START();
@@ -3966,7 +4120,7 @@ AVR_DI void substep_a_env(const KModel &m, EnvLDS &L, float *__restrict__ state,
     if (gld(env_cs(m, env) + CS_COOP) != 0.f) {
         float *ws = env_ws(m, env);
         const int rot = __float_as_int(gld(ws + WS_COOPROT));
-        demand = np_coop(m, env_cs(m, env), __float_as_int(gld(env_cs(m, env) + CS_NSP)), *reinterpret_cast<EpaBuf *>(&L), rot,
+        demand = np_coop<WSM>(m, env_cs(m, env), __float_as_int(gld(env_cs(m, env) + CS_NSP)), *reinterpret_cast<EpaBuf *>(&L), rot,
                          persist ? AVR_COOP_CAP : 1 << 30);
         if (lane_id() == 0) ws[WS_COOPROT] = __int_as_float(rot + AVR_COOP_CAP);
         SYNC();
@@ -3998,11 +4152,12 @@ AVR_DI void substep_a_env(const KModel &m, EnvLDS &L, float *__restrict__ state,
     WT_END(0);
 }
 
+template <int WSM>
 __global__ __launch_bounds__(64) AVR_KATTR void avr_substep_a_kernel(const KModel *__restrict__ mp, float *__restrict__ state,
                                                                      const unsigned char *__restrict__ mask, float dt, int env0, int n_envs) {
     __shared__ EnvLDS L;
     AVR_ENV_GUARD();
-    substep_a_env(m, L, state, dt, env, n_envs);
+    substep_a_env<WSM>(m, L, state, dt, env, n_envs);
 }
 
 // ---------------------------------------------------------------------------- part B: PGS solve
@@ -5163,7 +5318,9 @@ hipError_t avr_launch_step(const KModel *h_m, const KModel *d_m, float *state, c
         hipLaunchKernelGGL(avr_coop_kernel, dim3(n_envs), dim3(64), 0, stream, d_m, mask, env0, env1);
 #endif
         mark(AVR_K_A);
-        hipLaunchKernelGGL(avr_substep_a_kernel, dim3(n_envs), dim3(64), 0, stream, d_m, state, mask, h, env0, env1);
+        // (the instance with the cooperative path's wave-wide supports, or the one without them)
+        if (h_m->coop_wsup) hipLaunchKernelGGL(avr_substep_a_kernel<1>, dim3(n_envs), dim3(64), 0, stream, d_m, state, mask, h, env0, env1);
+        else hipLaunchKernelGGL(avr_substep_a_kernel<0>, dim3(n_envs), dim3(64), 0, stream, d_m, state, mask, h, env0, env1);
         mark(AVR_K_B);
         hipLaunchKernelGGL(avr_substep_b4_kernel, dim3(8 * ((n_envs + 31) / 32)), dim3(64), 0, stream, d_m, state, mask, h, frame_end, env0, env1);
     };
@@ -5184,10 +5341,16 @@ hipError_t avr_launch_step(const KModel *h_m, const KModel *d_m, float *state, c
             for (int k = 0; k < nsub; k++) sub(dt, k == nsub - 1);
     }
     mark(AVR_K_TASK);
-    hipLaunchKernelGGL(avr_task_kernel, dim3(n_envs), dim3(64), 0, stream, d_m, state, obs, rew, done, info, mask, mode, env0, env1);
 #if AVR_TASK == AVR_TASK_BEDBATH
-    if (mode == MODE_STEP || mode == MODE_STEP_RANDOM)      // stalled closest-distance pairs (avr_glue_bedbath.hip)
-        hipLaunchKernelGGL(avr_bb_stall_kernel, dim3(n_envs), dim3(64), 0, stream, d_m, state, rew, mask, env0, env1);
+    // (BedBathing's closest-distance query holds cooperative pairs: two instances, as kernel a)
+    if (h_m->coop_wsup) hipLaunchKernelGGL(avr_task_kernel<1>, dim3(n_envs), dim3(64), 0, stream, d_m, state, obs, rew, done, info, mask, mode, env0, env1);
+    else hipLaunchKernelGGL(avr_task_kernel<0>, dim3(n_envs), dim3(64), 0, stream, d_m, state, obs, rew, done, info, mask, mode, env0, env1);
+    if (mode == MODE_STEP || mode == MODE_STEP_RANDOM) {    // stalled closest-distance pairs (avr_glue_bedbath.hip)
+        if (h_m->coop_wsup) hipLaunchKernelGGL(avr_bb_stall_kernel<1>, dim3(n_envs), dim3(64), 0, stream, d_m, state, rew, mask, env0, env1);
+        else hipLaunchKernelGGL(avr_bb_stall_kernel<0>, dim3(n_envs), dim3(64), 0, stream, d_m, state, rew, mask, env0, env1);
+    }
+#else
+    hipLaunchKernelGGL(avr_task_kernel, dim3(n_envs), dim3(64), 0, stream, d_m, state, obs, rew, done, info, mask, mode, env0, env1);
 #endif
     mark(-1);
     return hipGetLastError();
@@ -5253,8 +5416,14 @@ hipError_t avr_launch_random_actions(unsigned long long seed, int env_offset, lo
 
 // [vgprs, 0, lds bytes, scratch bytes] of each kernel of a step: pairs, narrowphase, a, b4, task
 hipError_t avr_kernel_attrs(int *out20) {
-    const void *k[5] = {(const void *)avr_substep_pairs_kernel, (const void *)avr_narrowphase_kernel, (const void *)avr_substep_a_kernel,
-                        (const void *)avr_substep_b4_kernel, (const void *)avr_task_kernel};
+    // (kernel a, and BedBathing's task kernel: the instance of the task's default K_COOP_WSUP)
+#if AVR_TASK == AVR_TASK_BEDBATH
+    const void *task_k = (const void *)avr_task_kernel<K_COOP_WSUP>;
+#else
+    const void *task_k = (const void *)avr_task_kernel;
+#endif
+    const void *k[5] = {(const void *)avr_substep_pairs_kernel, (const void *)avr_narrowphase_kernel, (const void *)avr_substep_a_kernel<K_COOP_WSUP>,
+                        (const void *)avr_substep_b4_kernel, task_k};
     for (int i = 0; i < 5; i++) {
         hipFuncAttributes a;
         hipError_t e = hipFuncGetAttributes(&a, k[i]);

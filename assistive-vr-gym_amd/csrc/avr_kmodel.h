@@ -144,6 +144,8 @@ struct KModel {
                                // (AVR_PAIRS_FLAT=0|1; per-task default K_PAIRS_FLAT), else one compound pair at a time
     int np_hot;                // the narrowphase's sphere-hull blocks start the pairs of the env's contact pool first
                                // (AVR_NP_HOT=0|1; per-task default K_NP_HOT), else list order
+    int coop_wsup;             // the wave-cooperative narrowphase takes a hull's support point wave-wide: one vertex (or table
+                               // candidate) per lane (AVR_COOP_WSUP=0|1; per-task default K_COOP_WSUP), else the serial scans
     float *dynho;              // per-env dynamics hand-over between the dynamics role and kernel a: [n_envs][HO_WORDS]
     float *ws;                 // per-env workspace between sub-step kernels: [n_envs][128]
     float *cscr;               // per-env collision scratch between the part-A kernels: [n_envs][CS_WORDS]

@@ -52,6 +52,7 @@
 #define K_PAIRS_FLAT 1          // flat child-pair enumeration in the pair kernel (KModel.pairs_flat's default)
 #define K_NP_HOT 1              // the narrowphase starts the contact pool's sphere-hull pairs first (KModel.np_hot's default)
 #define K_B4_FIXED 1            // part B's fixed-cost trims on the LDS row sources (avr_kernel.hip B4_FIXED's default)
+#define K_COOP_WSUP 1           // wave-wide hull supports on the cooperative narrowphase path (KModel.coop_wsup's default)
 #elif AVR_TASK == AVR_TASK_SCRATCH || AVR_TASK == AVR_TASK_BEDBATH
 // the PR2 family: ScratchItchPR2 and BedBathingPR2 share the state layout (AVR_SI_*)
 #define K_PR2 1
@@ -60,6 +61,8 @@
 #define K_PAIRS_FLAT 1          // flat child-pair enumeration in the pair kernel (KModel.pairs_flat's default)
 #define K_NP_HOT 0              // the narrowphase keeps list order (KModel.np_hot's default: the reorder gains nothing on the PR2 tasks)
 #define K_B4_FIXED 0            // part B as it was (B4_FIXED's default: the trims lose 0.6 to 2 % on the PR2 tasks)
+#define K_COOP_WSUP 0           // the cooperative narrowphase keeps the serial support scans (KModel.coop_wsup's default: on gains
+                                // nothing measurable on the PR2 tasks, profiles/coop_support_ab.json)
 #define K_MAX_LINKS AVR_SI_MAX_LINKS
 #define K_MAX_DOF AVR_SI_MAX_DOF
 #define K_HC_N AVR_SI_HC_N

@@ -455,6 +455,12 @@ int32_t avr_pairs_flat(const avr_sim *sim);
  * overrides), else 0: list order.  Results are stored by pair index and do not depend on it.  No
  * reference counterpart (diagnostic). */
 int32_t avr_np_hot(const avr_sim *sim);
+/* 1 when the wave-cooperative narrowphase (EPA, the GJK reruns in double, big hulls) takes a hull's
+ * support point wave-wide: a hull of at most 64 vertices one vertex per lane from registers, a larger
+ * table hull its cell's candidates one per lane (the task's default, AVR_COOP_WSUP=0|1 in the
+ * environment at avr_create overrides), else 0: the serial scans.  The support vertex, and so every
+ * result, is the same either way.  No reference counterpart (diagnostic). */
+int32_t avr_coop_wsup(const avr_sim *sim);
 /* Graph captures made by this handle so far (each distinct step key captures once; a few keys
  * are cached).  No reference counterpart (diagnostic). */
 int64_t avr_graph_captures(avr_sim *sim);

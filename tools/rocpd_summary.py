@@ -62,8 +62,8 @@ def counters(c, names):
     res = {}
     for k in STEP_KERNELS:
         for n in names:
-            v = [r[0] for r in c.execute("select value from counters_collection where counter_name=? and (kernel_name like ? or kernel_name like ?)",
-                                         (n, k + '(%', '%::' + k + '(%'))]
+            v = [r[0] for r in c.execute("select value from counters_collection where counter_name=? and (kernel_name like ? or kernel_name like ? or kernel_name like ?)",
+                                         (n, k + '(%', '%::' + k + '(%', '%::' + k + '<%'))]      # (<: a templated kernel's instance)
             if v:
                 res.setdefault(k, {})[n] = float(np.median(v))
     return res
